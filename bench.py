@@ -3,6 +3,7 @@
 (slope + aspect + flats + section/proportion + UCA sweep + TWI) on synthetic DEM tiles.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts its own N ranks)
+    python bench.py ... --dump-outputs DIR                 (also writes a fixed sample of the last step's outputs: DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W        (any launcher that sets RANK / LOCAL_RANK / WORLD_SIZE)
 
@@ -52,7 +53,45 @@ def parse():
     ap.add_argument('--config', type=int, default=3, choices=[2, 3, 5],
                     help='BASELINE.json config: 3 = the headline line (default); 2 = 4096^2 stencil kernel only; 5 = 8192^2 int16 with the '
                          'reference defaults (conditioning on the device).  2 and 5 are single-GPU side lines, stored under profiles/')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64): '
+                         'a fixed, seeded sample of at most %d cells per tile (DIR/sample_index.npy: flat row-major indices)' % DUMP_CELLS)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+DUMP_CELLS = 3 << 18           # sampled cells per tile: index 8 + 4 float64 fields + their 4 float32 codes + 2 float32 masks = 64 B/cell, 48 MB
+DUMP_SEED = 12345
+
+
+def dump_outputs(path, shape, fields, n_tiles=1):
+    """Write the outputs of the last timed step for comparing two builds output for output: every field of `fields`
+    ([(name, array-getter, dtype)]) sampled at the same seeded cells of a tile of `shape` (all cells when the tile has at most
+    DUMP_CELLS / n_tiles of them), as path/<name>.npy in float32 / float64, plus the sample's flat row-major indices.  Every
+    file holds finite numbers only: a float64 field's NaN / +inf / -inf cells (TWI is NaN on flats, as in the reference) are 0
+    in <name>.npy and coded 1 / 2 / 3 in <name>_nonfinite.npy (0: finite).  Each array is read and released in turn."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cells = int(np.prod(shape))
+    k = max(1, DUMP_CELLS // n_tiles)
+    idx = np.arange(cells) if cells <= k else np.sort(np.random.default_rng(DUMP_SEED).choice(cells, k, replace=False))
+    tmp = os.path.join(path, '.sample_index.%d.npy' % os.getpid())      # (the ranks of one run share the directory)
+    np.save(tmp, idx.astype(np.float64))
+    os.replace(tmp, os.path.join(path, 'sample_index.npy'))
+    for name, get, dtype in fields:
+        a = np.asarray(get())
+        assert a.shape == tuple(shape), (name, a.shape, shape)
+        v = a.reshape(-1)[idx].astype(dtype)
+        del a
+        if dtype == np.float64:
+            code = np.zeros(v.shape, np.float32)
+            code[np.isnan(v)], code[np.isposinf(v)], code[np.isneginf(v)] = 1, 2, 3
+            v[code != 0] = 0.0
+            np.save(os.path.join(path, name + '_nonfinite.npy'), code)
+        assert np.isfinite(v).all(), name
+        np.save(os.path.join(path, name + '.npy'), v)
 
 
 def make_options(_ffi, drain_pits):
@@ -106,14 +145,17 @@ def cpu_baseline(size, seed, drain_pits):
 
 def run_config2(args):
     """BASELINE.json config 2: 4096 x 4096 fp64 fractal, the slope / aspect stencil kernel only."""
+    import numpy as np
     from pydem_amd import DEMProcessor
     n = 4096
     dp = DEMProcessor.from_synthetic((n, n), dict(seed=0), dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False)
     dp.run_slopes_directions()
     tile = dp._tile
     tile.bench_stencil(max(args.warmup, 20))
-    iters = max(args.steps, 200)
+    iters = args.steps
     ms = tile.bench_stencil(iters)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, (n, n), [('slope', lambda: dp.mag, np.float64), ('aspect', lambda: dp.direction, np.float64)])
     cells = float(n) * n
     achieved = STENCIL_BYTES_PER_CELL * cells / (ms * 1e-3) / 1e9
     print(json.dumps({
@@ -164,6 +206,10 @@ def run_config5(args):
         step()
     dts = [step() for _ in range(args.steps)]
     dt = sum(dts) / len(dts)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, (n, n), [('elev', lambda: dp.elev, np.float64), ('slope', lambda: dp.mag, np.float64),
+                                                 ('aspect', lambda: dp.direction, np.float64), ('uca', lambda: dp.uca, np.float64),
+                                                 ('twi', lambda: dp.twi, np.float64)])
     tm = dp._tile.timings()
     cells = float(n) * n
     st_ms = tm['stencil_kernel_ms']
@@ -348,6 +394,7 @@ def main():
     world = int(os.environ.get('WORLD_SIZE', '1'))
     import warnings
     warnings.simplefilter('ignore')
+    import numpy as np
     from pydem_amd import _ffi, process_manager
     n = m = args.size
     ndev = _ffi.device_count()
@@ -440,6 +487,19 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # per-tile results as ProcessManager.tile_result hands them out (before anything below re-launches a kernel)
+        for i in mine:
+            pre = '' if pm.n_inputs == 1 else 't%02d_' % i
+            fields = [(pre + key, (lambda key=key, i=i: pm.tile_result(i, key)), np.float64) for key in ('slope', 'aspect', 'uca_total', 'twi')]
+            fields += [(pre + key, (lambda key=key, i=i: pm.tile_result(i, key)), np.float32) for key in ('edge_todo', 'edge_done')]
+            dump_outputs(args.dump_outputs, (n, m), fields, pm.n_inputs)
+            dp = pm.tiles[i]
+            for key in ('mag', 'direction', 'uca', 'edge_todo', 'edge_done'):
+                if key in dp._on_device:
+                    dp._host.pop(key, None)       # (the host copies the reads above made of device-resident fields)
+            if dp._twi_on_device:
+                dp._twi10 = None
     if world > 1:
         dt = pm.transport.allreduce_max(dt)
         per_rank = group.all_gather_object({"rank": rank, "edge_waves": int(pm.edge_waves), "edge_rounds_run_here": len(pm.edge_round_log),

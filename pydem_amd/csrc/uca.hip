@@ -3383,7 +3383,7 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
                 const int grid = (int)(ntiles * 2 < 2048 ? (ntiles * 2 > 64 ? ntiles * 2 : 64) : 2048);
                 for (int b = 0; b < batch; b++, p++) {
                     N.list = tile_list[(p + 1) % 2]; N.count = &cntT[(p + 1) % 3];
-                    hipLaunchKernelGGL(k_sweep_tiles_listed, dim3(grid), dim3(256), 0, t->stream, A, (uint32_t)p, tiles_x,
+                    hipLaunchKernelGGL(k_sweep_tiles_listed, dim3(grid), dim3(64 * LWPB), 0, t->stream, A, (uint32_t)p, tiles_x,
                                        (const int32_t *)tile_list[p % 2], (const int32_t *)&cntT[p % 3], tile_done, total, N,
                                        &cntT[(p + 2) % 3], work3, Y);
                     launches++;

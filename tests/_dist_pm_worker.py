@@ -22,6 +22,7 @@ def main():
     from pydem_amd.parallel import DistTransport
     name, path = sys.argv[1], sys.argv[2]
     mode = sys.argv[3] if len(sys.argv) > 3 else 'reference'
+    width = int(sys.argv[5]) if len(sys.argv) > 5 else world               # pool width (default: one worker per rank)
     on_device = len(sys.argv) > 4 and sys.argv[4] in ('device', 'rccl')     # the HIP processor ('device': both ranks share the box's one GPU)
     use_rccl = len(sys.argv) > 4 and sys.argv[4] == 'rccl'                  # one GPU per rank, the edge board refreshed by ncclAllReduce
     pkw = {} if on_device else {'processor_cls': OracleProcessor}
@@ -31,7 +32,7 @@ def main():
     dkw = {k: v for k, v in g['kwargs'].items() if k not in ('ny_grid', 'nx_grid', 'overlap')}
     process_manager.DEBUG = True
     pm = process_manager.ProcessManager(in_path=path, dem_proc_kwargs=dkw, elev_conditioned=True, transport=False,
-                                        n_workers=(1 if mode == 'reference' else world), edge_mode=mode, **pkw)
+                                        n_workers=(1 if mode == 'reference' else width), edge_mode=mode, **pkw)
     if use_rccl:
         from pydem_amd.parallel import make_rccl_transport
         pm.transport = make_rccl_transport(pm, pkw['devices'][0], group)
@@ -47,7 +48,7 @@ def main():
     if mode == 'pool':
         # pool mode is checked against the single-process pool run of the same mosaic: same waves, identical results
         # (what the waves converge to is tested in tests/test_process_manager_pool.py)
-        pm1 = process_manager.ProcessManager(in_path=path, dem_proc_kwargs=dkw, elev_conditioned=True, n_workers=world, edge_mode='pool',
+        pm1 = process_manager.ProcessManager(in_path=path, dem_proc_kwargs=dkw, elev_conditioned=True, n_workers=width, edge_mode='pool',
                                              **{k: v for k, v in pkw.items() if k != 'devices'})
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')

@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_reference_import_names_resolve_to_pydem_amd():
+def test_reference_import_names_resolve_to_pydem_amd(tmp_path):
     code = (
         "import pydem, pydem_amd\n"
         "from pydem.dem_processing import DEMProcessor\n"
@@ -20,7 +20,7 @@ def test_reference_import_names_resolve_to_pydem_amd():
         "assert cyutils.drain_area is cy.drain_area and cyutils.drain_connections is cy.drain_connections\n"
         "print('ok')\n")
     env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, 'compat'))
-    out = subprocess.run([sys.executable, '-c', code], env=env, cwd='/tmp', capture_output=True, text=True, timeout=120)
+    out = subprocess.run([sys.executable, '-c', code], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == 'ok', out.stderr
 
 

@@ -1,7 +1,8 @@
 """The alternative sweep schedules (the LDS-resident first pass, PYDEM_SWEEP_FIRST=lds; resident / generic visits; the two-level
 solve of the tail at several switch points, PYDEM_SWEEP_SYM) must give the same answers as the default tile-pass schedule.  The mode is read once per process, hence the subprocess.  The frontier-queue
-schedule (PYDEM_SWEEP_MODE=queue) only exists in a diagnostic build of the library (PYDEM_HIPCC_FLAGS=-DPYDEM_SWEEP_QUEUE: it
-refuses some valid inputs, so a product build ignores the variable); its cases run with PYDEM_TEST_SWEEP_QUEUE=1."""
+schedule (PYDEM_SWEEP_MODE=queue) only exists in a diagnostic build of the library (-DPYDEM_SWEEP_QUEUE: it refuses some valid
+inputs, so a product build ignores the variable); build() links that build as pydem_amd/lib/libpydem_hip_queue.so, and the
+queue cases point the subprocess's binding at it before anything loads the library."""
 import os
 import subprocess
 import sys
@@ -15,6 +16,7 @@ import sys, warnings
 import numpy as np
 sys.path.insert(0, %(root)r)
 warnings.simplefilter('ignore')
+%(use_lib)s
 from oracle import oracle as O
 from pydem_amd import DEMProcessor, synth
 for shape, seed in (((700, 520), 41), ((1024, 1024), 42)):
@@ -26,16 +28,23 @@ for shape, seed in (((700, 520), 41), ((1024, 1024), 42)):
     assert np.allclose(dp.uca, o.uca, rtol=1e-9, atol=0, equal_nan=True)
     assert np.array_equal(dp.edge_todo, o.edge_todo) and np.array_equal(dp.edge_done, o.edge_done)
 print("MODES-OK", dp.timings['sweep_rounds'], dp.timings['sweep_kernel_launches'])
+%(check_lib)s
 '''
 
+# the queue cases: the binding of the subprocess loads the diagnostic build (and the script checks that it did)
+USE_QUEUE_LIB = "from pydem_amd import _ffi, build as _b; assert _ffi._lib is None; _ffi.LIB_PATH = _b.QUEUE_LIB"
+CHECK_QUEUE_LIB = "assert _ffi._lib._name == _b.QUEUE_LIB, _ffi._lib._name"
 
-QUEUE_BUILD = os.environ.get('PYDEM_TEST_SWEEP_QUEUE') == '1'
-needs_queue_build = pytest.mark.skipif(not QUEUE_BUILD, reason="the queue schedule needs a library built with -DPYDEM_SWEEP_QUEUE (PYDEM_TEST_SWEEP_QUEUE=1)")
+
+def queue_lib():
+    from pydem_amd import build
+    assert os.path.exists(build.QUEUE_LIB), "the diagnostic queue build is missing (%s): build() makes it" % build.QUEUE_LIB
+    return build.QUEUE_LIB
 
 
-@pytest.mark.parametrize('env', [pytest.param({'PYDEM_SWEEP_MODE': 'queue'}, marks=needs_queue_build),
-                                 pytest.param({'PYDEM_SWEEP_MODE': 'queue', 'PYDEM_SWEEP_TILE_SWITCH': '0'}, marks=needs_queue_build),
-                                 pytest.param({'PYDEM_SWEEP_MODE': 'queue', 'PYDEM_TILE_PASSES': '3'}, marks=needs_queue_build),
+@pytest.mark.parametrize('env', [{'PYDEM_SWEEP_MODE': 'queue'},
+                                 {'PYDEM_SWEEP_MODE': 'queue', 'PYDEM_SWEEP_TILE_SWITCH': '0'},
+                                 {'PYDEM_SWEEP_MODE': 'queue', 'PYDEM_TILE_PASSES': '3'},
                                  {'PYDEM_SWEEP_FIRST': 'lds'},           # pass 1 by the LDS-resident kernel (csrc/uca.hip K5a)
                                  {'PYDEM_SWEEP_DENSE': '3'},             # three dense level kernels ahead of the tile passes (K5d)
                                  {'PYDEM_SWEEP_SYM': '0'},               # tile passes only: no two-level solve for the tail (K5f, csrc/uca_sym.inl)
@@ -47,18 +56,25 @@ needs_queue_build = pytest.mark.skipif(not QUEUE_BUILD, reason="the queue schedu
 def test_queue_schedule_matches_oracle(env):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     e = dict(os.environ); e.update(env)
-    r = subprocess.run([sys.executable, '-c', SCRIPT % {'root': root}], env=e, capture_output=True, text=True, timeout=600)
+    queue = env.get('PYDEM_SWEEP_MODE') == 'queue'
+    if queue:
+        queue_lib()
+    script = SCRIPT % {'root': root, 'use_lib': USE_QUEUE_LIB if queue else '', 'check_lib': CHECK_QUEUE_LIB if queue else ''}
+    r = subprocess.run([sys.executable, '-c', script], env=e, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and 'MODES-OK' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-@needs_queue_build
 def test_circular_drainage_replay_in_queue_schedule():
     """The re-seed replay over the cells on / below a drainage loop (csrc/uca.hip K5c) runs after either schedule: the
-    hand-made loop fields of tests/test_gpu_parity.py, once more with PYDEM_SWEEP_MODE=queue."""
+    hand-made loop fields of tests/test_gpu_parity.py, once more with PYDEM_SWEEP_MODE=queue on the queue build."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    queue_lib()
     e = dict(os.environ, PYDEM_SWEEP_MODE='queue')
-    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(root, 'tests', 'test_gpu_parity.py'), '-q', '-x', '-k', 'circular_drainage'],
-                       env=e, capture_output=True, text=True, timeout=600, cwd=root)
+    script = "\n".join(["import sys, pytest", "sys.path.insert(0, %r)" % root, USE_QUEUE_LIB,
+                         "rc = pytest.main([%r, '-q', '-x', '-p', 'no:cacheprovider', '-k', 'circular_drainage'])"
+                         % os.path.join(root, 'tests', 'test_gpu_parity.py'),
+                         CHECK_QUEUE_LIB, "sys.exit(int(rc))"])
+    r = subprocess.run([sys.executable, '-c', script], env=e, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0 and ' passed' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
