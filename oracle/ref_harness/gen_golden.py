@@ -233,6 +233,30 @@ def conditioning_cases():
     run_and_save('g7_nan_sea', s2, 25.0, 25.0, dict())
 
 
+def reach_cases():
+    """drain_pits_max_dist=None (the reference's `allow_none` reach, dem_processing.py:118): a flat channel of 300+ rows whose
+    pits drain 2..300 rows away, so the dX / dY sums of the pit -> drain distances (:1346-1348, :1993-1997) run numpy's
+    pairwise split (slices over 128) -- terrain: tests/capacity_terrain.py"""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import capacity_terrain as CT
+    z, info = CT.channel_plateau(320)
+    dXv, dYv = CT.spacing(z.shape[0], seed=1)
+    kw = dict(fill_flats=False, drain_pits_path=False, drain_pits_max_dist=None)
+    rec = run_case(z, dXv, dYv, **kw)
+    span = CT.row_spans(rec['pit_i'], rec['pit_j'], z.shape[1])
+    assert span.max() > 256 and ((span > 128) & (span <= 137)).any() and (span <= 8).any(), span.max()
+    save('g5_opt_reach_none', rec, kw)
+    # calc_pit_drain_paths walks the channel from the strict minimum at its head to the opening 300 rows below
+    zp, info = CT.channel_plateau(300, pit_at_head=True)
+    dXv, dYv = CT.spacing(zp.shape[0], seed=2)
+    for name, kw in (('g7_reach_none_paths', dict(fill_flats=False, drain_pits_max_dist=None)),
+                     ('g7_reach_none_defaults', dict(drain_pits_max_dist=None))):
+        rec = run_case(zp, dXv, dYv, **kw)
+        rows = np.nonzero((rec['elev_drained'] != rec['elev_filled' if 'elev_filled' in rec else 'in_elev']).any(axis=1))[0]
+        assert rows.size and rows.max() - rows.min() > 128, rows
+        save(name, rec, kw)
+
+
 def run_and_save(name, elev, dX, dY, kw):
     save(name, run_case(elev, dX, dY, **kw), kw)
 
@@ -240,6 +264,10 @@ def run_and_save(name, elev, dX, dY, kw):
 def main():
     if '--only-conditioning' in sys.argv:
         conditioning_cases()
+        write_manifest()
+        return
+    if '--only-reach' in sys.argv:
+        reach_cases()
         write_manifest()
         return
     if '--only-edge' in sys.argv:
@@ -356,6 +384,7 @@ def main():
 
     edge_cases()
     conditioning_cases()
+    reach_cases()
     write_manifest()
 
 

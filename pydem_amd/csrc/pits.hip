@@ -300,12 +300,12 @@ __device__ __forceinline__ void finish_pit_wave(const PitParams &P, int32_t pit,
     }
 }
 
-// One pit.  W = window edge (multiple of 32), MAXD = drain list capacity.
-// region / border / promote: W*W-bit bitmaps; dlist/dxy/sv: drain scratch.
-template <int NT, int W, int MAXD>
+// One pit.  W = window edge (multiple of 32), maxd = drain list capacity.
+// region / border / promote: W*W-bit bitmaps; dlist/dxy/sv: drain scratch of maxd entries.
+template <int NT, int W>
 __device__ void solve_pit(const PitParams &P, int32_t pit, int gl, uint32_t *region, uint32_t *border, uint32_t *promote,
                           int32_t *dlist, double *dxy, double *sv, double *redd, int *redi, int *flag,
-                          int32_t &chunk_base, int32_t &chunk_left, PwFrame *stk)
+                          int32_t &chunk_base, int32_t &chunk_left, PwFrame *stk, int maxd)
 {
     constexpr int WORDS = W * W / 32;
     constexpr int WPR = W / 32;                    // words per window row
@@ -398,7 +398,7 @@ __device__ void solve_pit(const PitParams &P, int32_t pit, int gl, uint32_t *reg
             }
             int excl;
             const int tot = group_sum<NT>(cnt, redi, gl, &excl);
-            if (tot > MAXD) { if (gl == 0) flag[0] = 1; group_sync<NT>(); break; }
+            if (tot > maxd) { if (gl == 0) flag[0] = 2; group_sync<NT>(); break; }     // 2: the drain list, 1: the window
             int pos = excl;
             for (int w = w_lo; w < w_hi; w++) {
                 uint32_t b = border[w];
@@ -457,8 +457,9 @@ __device__ void solve_pit(const PitParams &P, int32_t pit, int gl, uint32_t *reg
     }
     group_sync<NT>();
     if (flag[0]) {                                                               // hand over to the large-window pass
+        // (the workgroup pass lists only the pits whose drains outgrew its list: a larger list cannot help one that left the window)
         if (gl == 0) {
-            if (P.overflow_list) P.overflow_list[atomicAdd(P.overflow_count, 1)] = pit;
+            if (P.overflow_list && flag[0] == 2) P.overflow_list[atomicAdd(P.overflow_count, 1)] = pit;
             else atomicAdd(&P.out_count[3], 1);
         }
         return;
@@ -1175,7 +1176,7 @@ __global__ __launch_bounds__(64) void k_pits_wave_big(PitParams P, const int32_t
 #endif
 constexpr int BLOCK_NT = PYDEM_BLOCK_NT;
 __global__ __launch_bounds__(BLOCK_NT) void k_pits_block(PitParams P, const int32_t *__restrict__ pits, const int32_t *npits,
-                                                    int32_t *g_dl, double *g_dxy, double *g_sv)
+                                                    int32_t *g_dl, double *g_dxy, double *g_sv, int maxd)
 {
     constexpr int WORDS = W_LARGE * W_LARGE / 32;
     extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
@@ -1186,9 +1187,9 @@ __global__ __launch_bounds__(BLOCK_NT) void k_pits_block(PitParams P, const int3
     int32_t chunk_base = 0, chunk_left = 0;
     const int32_t np = *npits;
     for (int32_t q = blockIdx.x; q < np; q += gridDim.x) {
-        solve_pit<BLOCK_NT, W_LARGE, MAXD_LARGE>(P, pits[q], threadIdx.x, dyn, dyn + WORDS, dyn + 2 * WORDS,
-                                             g_dl + (size_t)blockIdx.x * MAXD_LARGE, g_dxy + (size_t)blockIdx.x * MAXD_LARGE,
-                                             g_sv + (size_t)blockIdx.x * MAXD_LARGE, redd, redi, flag, chunk_base, chunk_left, stk);
+        solve_pit<BLOCK_NT, W_LARGE>(P, pits[q], threadIdx.x, dyn, dyn + WORDS, dyn + 2 * WORDS,
+                                     g_dl + (size_t)blockIdx.x * maxd, g_dxy + (size_t)blockIdx.x * maxd,
+                                     g_sv + (size_t)blockIdx.x * maxd, redd, redi, flag, chunk_base, chunk_left, stk, maxd);
         __syncthreads();
     }
 }
@@ -1536,19 +1537,30 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
             // (function attributes are per device, and tiles of several devices / threads come through here: set it
             // every time -- the call is cheap next to a 640 x 640 window search)
             HIP_TRY(hipFuncSetAttribute((const void *)k_pits_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-            const size_t need = (size_t)gb * MAXD_LARGE * (4 + 8 + 8);
-            if (t->scratch_bytes < need) {
-                if (t->scratch) { HIP_TRY(hipFree(t->scratch)); t->device_bytes -= (int64_t)t->scratch_bytes; }
-                HIP_TRY(dev_malloc((void **)&t->scratch, need));
-                t->scratch_bytes = need; t->device_bytes += (int64_t)need;
-            }
-            double *g_dxy = (double *)t->scratch;
-            double *g_sv = g_dxy + (size_t)gb * MAXD_LARGE;
-            int32_t *g_dl = (int32_t *)(g_sv + (size_t)gb * MAXD_LARGE);
-            P.overflow_list = nullptr; P.overflow_count = nullptr;
-            hipLaunchKernelGGL(k_pits_block, dim3(gb), dim3(BLOCK_NT), dyn, t->stream, P, t->queue[0], cnt + 9, g_dl, g_dxy, g_sv);
-            HIP_TRY(hipMemcpyAsync(t->h_counters, cnt, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-            HIP_TRY(hipStreamSynchronize(t->stream));
+            // drain scratch: MAXD_LARGE entries per workgroup; a pit with more drains (its border can hold up to the whole
+            // window, and the reference takes them all) is listed and solved again below with room for a full window
+            auto launch_block = [&](int blocks, int maxd, const int32_t *list, const int32_t *count) -> int {
+                const size_t need = (size_t)blocks * maxd * (4 + 8 + 8);
+                if (t->scratch_bytes < need) {
+                    if (t->scratch) { HIP_TRY(hipFree(t->scratch)); t->device_bytes -= (int64_t)t->scratch_bytes; }
+                    HIP_TRY(dev_malloc((void **)&t->scratch, need));
+                    t->scratch_bytes = need; t->device_bytes += (int64_t)need;
+                }
+                double *g_dxy = (double *)t->scratch;
+                double *g_sv = g_dxy + (size_t)blocks * maxd;
+                int32_t *g_dl = (int32_t *)(g_sv + (size_t)blocks * maxd);
+                hipLaunchKernelGGL(k_pits_block, dim3(blocks), dim3(BLOCK_NT), dyn, t->stream, P, list, count, g_dl, g_dxy, g_sv, maxd);
+                HIP_TRY(hipMemcpyAsync(t->h_counters, cnt, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+                HIP_TRY(hipStreamSynchronize(t->stream));
+                return 0;
+            };
+            HIP_TRY(hipMemsetAsync(cnt + 13, 0, sizeof(int32_t), t->stream));
+            P.overflow_list = t->labels; P.overflow_count = cnt + 13;              // (the input lists of passes 2 / 3 are dead)
+            PYDEM_TRY(launch_block(gb, MAXD_LARGE, t->queue[0], cnt + 9));
+            const int32_t n_retry = t->h_counters[13];
+            P.overflow_list = nullptr; P.overflow_count = nullptr;                 // what still does not fit: a capacity error
+            if (n_retry > 0) PYDEM_TRY(launch_block(n_retry < 4 ? n_retry : 4, W_LARGE * W_LARGE, t->labels, cnt + 13));
+            if (dbg_env) fprintf(stderr, "pits: %d pits with more than %d drains solved again with room for %d\n", n_retry, MAXD_LARGE, W_LARGE * W_LARGE);
         }
         HIP_TRY(hipGetLastError());
         const int64_t ne = t->h_counters[1];
