@@ -654,7 +654,7 @@ __device__ __forceinline__ double in_edge(const SweepArgs &A, int32_t c, int m, 
 // 64-bit add, per access.  The tile is wavefront-uniform, so the five planes get one SCALAR base each -- the address of the
 // halo's first cell (i0 - 1, j0 - 1), which for a tile on the grid's edge lies in front of the plane and is only ever
 // used with offsets of cells that exist -- and a lane addresses a cell by `h` = halo row * m + halo column (24-bit
-// multiply: full rate; stage_sweep refuses tiles wider than 2^24 columns), scaled to a 32-bit unsigned byte offset: the
+// multiply: full rate; stage_sweep refuses tiles of 2^22 columns or more), scaled to a 32-bit unsigned byte offset: the
 // loads and stores take the SGPR base + VGPR offset form.
 struct TileBase {
     const char *cinfo, *area, *contrib, *prop, *todo;

@@ -63,6 +63,18 @@ def check_fields(dp, want, cell_area):
     check_float('twi', dp.twi, want['twi'])
 
 
+def check_against_oracle_run(dp):
+    """cell by cell: the oracle's full path on the tile's (final) surface, run here, against every field of the device"""
+    from oracle import oracle as O
+    from pydem_amd import _ffi
+    from test_gpu_scale_paths import check_full_path
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        o = O.OracleDEM(np.asarray(dp.elev), dX=30.0, dY=30.0, drain_pits=True)
+        o.calc_twi()
+    check_full_path(dp, o, dp._tile.download(_ffi.TWI))
+
+
 @pytest.mark.parametrize('size', [1024, 16384])
 def test_config3_full_path_against_oracle_checksums(size):
     key = 'config3_%d' % size
@@ -75,6 +87,8 @@ def test_config3_full_path_against_oracle_checksums(size):
                                          drain_pits=True)
         dp.run_twi()
     check_fields(dp, SUMS[key], 900.0)
+    if size == 1024:
+        check_against_oracle_run(dp)
     if size == 16384:
         # the pit pairs above came through every pass of the search: the row pass (16 lanes per pit) ran by its default rule
         # (pits beyond the lane pass outnumber the resident wavefronts) and left only a small part to the wavefront pass
@@ -105,6 +119,8 @@ def test_config5_int16_defaults_against_oracle_checksums(size):
         dp.drain_pits_path = False
         dp.run_twi()
     check_fields(dp, want, 900.0)
+    if size == 1024:
+        check_against_oracle_run(dp)
 
 
 @pytest.mark.parametrize('n_workers', [1, 8])
