@@ -13,6 +13,8 @@
  *                             _calc_uca_chunk :864-987, _calc_uca_section_proportion :1021-1070,
  *                             _mk_adjacency_matrix :1072-1153, _mk_connectivity_pits :1269-1382 and
  *                             the native loop cyutils.drain_area   pydem/cyfuncs/cyutils.pyx:78-187
+ *   pydem_uca_weighted        the sweep of pydem_uca from a per-cell weight (_calc_uca_chunk :883-972, cyutils.pyx:78-187
+ *                             with the initial areas replaced; TauDEM AreaDinf with a weight grid) -- no reference method
  *   pydem_uca_edge_update     DEMProcessor.calc_uca(uca_init=, edge_init_data=) :724-771,
  *                             _calc_uca_chunk_update :778-862, cyutils.drain_connections
  *                             pydem/cyfuncs/cyutils.pyx:35-72
@@ -46,7 +48,9 @@ enum pydem_field {
     PYDEM_TWI = 7,         /* float64 [n,m]  ln(uca / (mag + min_slope)) (un-scaled)            */
     PYDEM_EDGE_TODO = 8,   /* uint8   [n,m]  inlet edge cells still waiting for a neighbour     */
     PYDEM_EDGE_DONE = 9,   /* uint8   [n,m]                                                    */
-    PYDEM_FIELD_COUNT = 10
+    PYDEM_WEIGHT = 10,     /* float64 [n,m]  per-cell weight of pydem_uca_weighted (upload; the call consumes it) */
+    PYDEM_UCA_WEIGHTED = 11, /* float64 [n,m]  weighted upstream accumulation, NaN on flats     */
+    PYDEM_FIELD_COUNT = 12
 };
 
 /* element types accepted by pydem_tile_upload for PYDEM_ELEV (held as float64 on the device; a PYDEM_F32 elevation
@@ -90,6 +94,7 @@ typedef struct pydem_timings {
     int64_t n_pits_row;           /* ... that entered the row pass (16 lanes per pit; 0: pass not run, PYDEM_PITS_ROW=0)  */
     int64_t n_pits_wave;          /* ... that entered the wavefront pass (128 x 128 window)                               */
     int64_t n_pits_big;           /* ... that entered the 256 x 256 wavefront pass or the workgroup pass behind it        */
+    double uca_weighted_ms;       /* last pydem_uca_weighted: seed, level re-arm and weighted sweep (the other fields keep pydem_uca's) */
 } pydem_timings;
 
 const char *pydem_hip_last_error(void);
@@ -153,6 +158,21 @@ int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
 int pydem_uca(pydem_tile *t, pydem_options *opt);
+/* Weighted flow accumulation: the sweep of pydem_uca over the same flow graph (pit -> drain edges, the on-edge skip and
+ * the circular-drainage re-seed loop included) started from a per-cell seed instead of the cell area --
+ *     W[c] = seed[c] + sum over in-edges u -> c of W[u] * factor(u -> c),   seed = w * dX2 * dY2 (scale_by_cell_area) or w,
+ * NaN on flats -- i.e. DEMProcessor._calc_uca_chunk (pydem/dem_processing.py:883-972) and cyutils._drain_area
+ * (pydem/cyfuncs/cyutils.pyx:78-187) with their initial area array (:885, :901) replaced, as AreaDinf with a weight grid
+ * does.  Weights: PYDEM_WEIGHT, uploaded before every call (any finite value, zero and negative included; the call scales
+ * the plane in place and consumes it); result: PYDEM_UCA_WEIGHTED.  With w = 1 the result is pydem_uca's uca bit for bit.
+ * The flow graph is the tile's when the last graph stage ran with the same graph options as `opt` (drain_pits, _min_border,
+ * _max_iter, _max_dist, _max_dist_XY); otherwise the call runs the graph stage of pydem_uca itself and does not keep the graph:
+ * mag / flats are put back as they were (the pit patch undone; a temporary 12 bytes per flat cell), and so are section,
+ * proportion and edge_todo when the tile holds them (a temporary copy, 10 bytes per cell); only the pit-edge list
+ * (pydem_tile_pit_edges) is then that of the graph built here.  No edge masks, twi_min_area is not
+ * touched; uca, every other field and all of pydem_uca's timings (the graph stage's included) stay as they were, the next
+ * edge round rebuilds its work state.  uca_weighted_ms: seed, level re-arm and weighted sweep, not the graph stage. */
+int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

@@ -12,10 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libpydem_hip.so')
 
 # enum pydem_field
-ELEV, MAG, DIRECTION, FLATS, SECTION, PROPORTION, UCA, TWI, EDGE_TODO, EDGE_DONE = range(10)
+ELEV, MAG, DIRECTION, FLATS, SECTION, PROPORTION, UCA, TWI, EDGE_TODO, EDGE_DONE, WEIGHT, UCA_WEIGHTED = range(12)
 FIELD_DTYPE = {ELEV: np.float64, MAG: np.float64, DIRECTION: np.float64, FLATS: np.uint8,
                SECTION: np.int8, PROPORTION: np.float64, UCA: np.float64, TWI: np.float64,
-               EDGE_TODO: np.uint8, EDGE_DONE: np.uint8}
+               EDGE_TODO: np.uint8, EDGE_DONE: np.uint8, WEIGHT: np.float64, UCA_WEIGHTED: np.float64}
 # enum pydem_dtype
 _DTYPES = {np.dtype('float64'): 0, np.dtype('float32'): 1, np.dtype('int16'): 2, np.dtype('int32'): 3,
            np.dtype('uint8'): 4, np.dtype('int8'): 5, np.dtype('bool'): 4}
@@ -38,7 +38,8 @@ class Timings(C.Structure):
                 ('sweep_ms', C.c_double), ('twi_ms', C.c_double), ('sweep_rounds', C.c_int64),
                 ('sweep_kernel_launches', C.c_int64), ('n_flats', C.c_int64), ('n_pit_edges', C.c_int64),
                 ('n_pits_undrained', C.c_int64), ('n_unresolved', C.c_int64), ('sweep_tile_passes', C.c_int64),
-                ('n_pits', C.c_int64), ('n_pits_row', C.c_int64), ('n_pits_wave', C.c_int64), ('n_pits_big', C.c_int64)]
+                ('n_pits', C.c_int64), ('n_pits_row', C.c_int64), ('n_pits_wave', C.c_int64), ('n_pits_big', C.c_int64),
+                ('uca_weighted_ms', C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -78,6 +79,7 @@ SYMBOLS = {
     'pydem_slopes_directions': (C.c_int, [_P]),
     'pydem_find_flats': (C.c_int, [_P]),
     'pydem_uca': (C.c_int, [_P, C.POINTER(Options)]),
+    'pydem_uca_weighted': (C.c_int, [_P, C.POINTER(Options), C.c_int]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_edge_update': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
     'pydem_uca_edge_round_inc': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
@@ -272,6 +274,9 @@ class Tile(object):
 
     def uca(self, opt):
         check(self.lib.pydem_uca(self._h, C.byref(opt)))
+
+    def uca_weighted(self, opt, scale_by_cell_area=True):
+        check(self.lib.pydem_uca_weighted(self._h, C.byref(opt), int(bool(scale_by_cell_area))))
 
     def build_graph(self, opt):
         check(self.lib.pydem_build_graph(self._h, C.byref(opt)))

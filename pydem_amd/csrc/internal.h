@@ -61,6 +61,7 @@ struct pydem_tile {
     hipEvent_t ev[8] = {};
     // fields
     double *elev = nullptr, *mag = nullptr, *dir = nullptr, *prop = nullptr, *uca = nullptr, *twi = nullptr;
+    double *weight = nullptr, *uca_w = nullptr;     // pydem_uca_weighted: weights (seeds once the call has scaled them), result
     uint8_t *flats = nullptr, *edge_todo = nullptr, *edge_done = nullptr, *flat0 = nullptr;
     int8_t *section = nullptr;
     bool have[PYDEM_FIELD_COUNT] = {};
@@ -108,6 +109,7 @@ struct pydem_tile {
     double *line_stage = nullptr;   // max(n, m) doubles: staging for column get/set
     void *lines_stage = nullptr; int lines_cap = 0;   // staging for pydem_tile_get_lines
     bool graph_valid = false;   // inmask/gflags/section/prop/pit lists match the resident elev/dir/flats
+    pydem_options graph_opt = {};   // the options the graph was built with (pydem_uca_weighted reuses it only for the same ones)
     void *scratch = nullptr; size_t scratch_bytes = 0;
     int64_t device_bytes = 0;
     pydem_timings tm = {};
@@ -148,6 +150,7 @@ int stage_flats(pydem_tile *t);
 int stage_section_graph(pydem_tile *t, const pydem_options *opt);
 int stage_pits(pydem_tile *t, const pydem_options *opt);
 int stage_sweep(pydem_tile *t, const pydem_options *opt);
+int stage_uca_weighted(pydem_tile *t, const pydem_options *opt, int scale_by_cell_area);
 int stage_twi(pydem_tile *t, const pydem_options *opt);
 int stage_edge_update(pydem_tile *t, const pydem_options *opt, const double *const data[4], const uint8_t *const done[4],
                       const uint8_t *const todo[4]);

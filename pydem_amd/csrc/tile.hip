@@ -244,6 +244,35 @@ __global__ void k_restore_pit_slopes(const int32_t *__restrict__ src, int64_t n,
         if (src[e] >= 0) mag[src[e]] = -1.0;      // unused output slots hold -1
 }
 
+// pydem_uca_weighted on a tile without a (current) flow graph: the graph stage patches mag / flats at the drained pits
+// (:1369-1371), and pits are flat cells (the pit search's candidates: flats && elev > 0).  Saving (cell, mag) of every flat
+// cell before the stage and writing both back afterwards restores the two planes exactly.
+__global__ void k_flat_save(const uint8_t *__restrict__ flats, const double *__restrict__ mag, int64_t NN, int32_t *__restrict__ cells,
+                            double *__restrict__ vals, int64_t cap, unsigned long long *count)
+{
+    for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < NN; c0 += (int64_t)gridDim.x * blockDim.x) {     // (uniform per workgroup)
+        const int64_t c = c0 + threadIdx.x;
+        const bool f = c < NN && flats[c] != 0;
+        const unsigned long long b = __ballot(f);
+        if (!b) continue;
+        const int lane = (int)__lane_id(), leader = __ffsll((long long)b) - 1;
+        unsigned long long base = 0;
+        if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(b));
+        base = __shfl(base, leader);
+        const int64_t k = (int64_t)base + __popcll(b & ((1ull << lane) - 1ull));
+        if (f && cells && k < cap) { cells[k] = (int32_t)c; vals[k] = mag[c]; }
+    }
+}
+
+__global__ void k_flat_restore(const int32_t *__restrict__ cells, const double *__restrict__ vals, int64_t n, double *__restrict__ mag,
+                               uint8_t *__restrict__ flats)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        mag[cells[k]] = vals[k];
+        flats[cells[k]] = 1;
+    }
+}
+
 template <typename S>
 __global__ void k_convert_to_f64(const S *__restrict__ src, double *__restrict__ dst, int64_t n)
 {
@@ -285,6 +314,8 @@ int field_ptr(pydem_tile *t, int field, void ***pp, size_t *elem)
         case PYDEM_TWI: *pp = (void **)&t->twi; *elem = 8; return 0;
         case PYDEM_EDGE_TODO: *pp = (void **)&t->edge_todo; *elem = 1; return 0;
         case PYDEM_EDGE_DONE: *pp = (void **)&t->edge_done; *elem = 1; return 0;
+        case PYDEM_WEIGHT: *pp = (void **)&t->weight; *elem = 8; return 0;
+        case PYDEM_UCA_WEIGHTED: *pp = (void **)&t->uca_w; *elem = 8; return 0;
     }
     pydem_set_error("unknown field id %d", field);
     return -2;
@@ -535,7 +566,7 @@ int pydem_tile_destroy(pydem_tile *t)
     // (a stage that returned early between the fork and the join of the side stream may have left kernels there that still
     // write edge_todo / todo_work / prop: the planes go to the free lists -- i.e. to the next tile -- only once both streams are idle)
     if (t->stream2) (void)hipStreamSynchronize(t->stream2);
-    void *ptrs[] = {t->elev, t->mag, t->dir, t->prop, t->uca, t->twi, t->flats, t->edge_todo, t->edge_done,
+    void *ptrs[] = {t->elev, t->mag, t->dir, t->prop, t->uca, t->twi, t->weight, t->uca_w, t->flats, t->edge_todo, t->edge_done,
                     t->flat0, t->section, t->dX, t->dY, t->dX2, t->dY2, t->rowtab, t->sec_theta, t->row_area, t->inmask,
                     t->gflags, t->todo_work, t->indeg, t->queue[0], t->queue[1], t->labels, t->flatlist,
                     t->counters, t->scratch, t->pits.src, t->pits.dst, t->pits.w, t->pits.in_src,
@@ -912,6 +943,102 @@ static int ensure_graph(pydem_tile *t, pydem_options *opt, const char *who)
     PYDEM_TRY(stage_section_graph(t, opt));
     t->graph_valid = true;
     t->have[PYDEM_SECTION] = t->have[PYDEM_PROPORTION] = true;
+    return 0;
+}
+
+// the options the graph stage reads (pydem_uca with other values would build another graph)
+static bool same_graph_options(const pydem_options &a, const pydem_options &b)
+{
+    if (!a.drain_pits && !b.drain_pits) return true;
+    const bool xy = (a.drain_pits_max_dist_XY == b.drain_pits_max_dist_XY) ||
+                    (a.drain_pits_max_dist_XY != a.drain_pits_max_dist_XY && b.drain_pits_max_dist_XY != b.drain_pits_max_dist_XY);
+    return a.drain_pits == b.drain_pits && a.drain_pits_min_border == b.drain_pits_min_border &&
+           a.drain_pits_max_iter == b.drain_pits_max_iter && a.drain_pits_max_dist == b.drain_pits_max_dist && xy;
+}
+
+namespace {
+struct DevScratch {                     // a temporary device block that is freed on every way out
+    void *p = nullptr;
+    ~DevScratch() { if (p) (void)hipFree(p); }
+};
+}
+
+int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    PYDEM_TRY(need(t, PYDEM_WEIGHT, "pydem_uca_weighted"));
+    const pydem_timings keep = t->tm;   // pydem_uca's timings, the graph stage's included, are put back at the end
+    // The tile's flow graph when it is the one pydem_uca would build now; otherwise the graph stage runs here.  That stage patches
+    // the drained pits into mag / flats (:1369-1371), which the finalisation reads; the planes are put back afterwards (exactly:
+    // the patched cells are flat cells, saved with their slopes beforehand, 12 bytes per flat cell) and the graph is dropped
+    // (graph_valid pairs a graph with the PATCHED planes, as pydem_uca leaves them), so every call on such a tile starts from
+    // the same surface and a later pydem_uca / edge round builds its own graph.
+    const bool own_graph = !t->graph_valid || !same_graph_options(t->graph_opt, *opt);
+    DevScratch save, planes;
+    struct Kept { void *dst; size_t bytes; size_t off; };
+    std::vector<Kept> kept;             // resident results the graph stage overwrites (a tile where pydem_uca ran with other options)
+    int32_t *save_cells = nullptr;
+    double *save_vals = nullptr;
+    int64_t nsave = 0;
+    if (own_graph) {
+        PYDEM_TRY(need(t, PYDEM_FLATS, "pydem_uca_weighted"));
+        PYDEM_TRY(need(t, PYDEM_MAG, "pydem_uca_weighted"));
+        PYDEM_TRY(ensure_fields(t, {PYDEM_EDGE_TODO, PYDEM_EDGE_DONE}));
+        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(t->counters + 62);      // (scratch of the sweep's counter block)
+        const int g = (int)(cdiv(t->NN, 256) < 4096 ? cdiv(t->NN, 256) : 4096);
+        HIP_TRY(hipMemsetAsync(cnt, 0, 8, t->stream));
+        hipLaunchKernelGGL(k_flat_save, dim3(g), dim3(256), 0, t->stream, (const uint8_t *)t->flats, (const double *)t->mag, t->NN,
+                           (int32_t *)nullptr, (double *)nullptr, (int64_t)0, cnt);
+        unsigned long long hn = 0;
+        HIP_TRY(hipMemcpyAsync(&hn, cnt, 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        nsave = (int64_t)hn;
+        if (nsave > 0) {
+            HIP_TRY(dev_malloc(&save.p, (size_t)nsave * 12));
+            save_vals = (double *)save.p;
+            save_cells = (int32_t *)((char *)save.p + (size_t)nsave * 8);
+            HIP_TRY(hipMemsetAsync(cnt, 0, 8, t->stream));
+            hipLaunchKernelGGL(k_flat_save, dim3(g), dim3(256), 0, t->stream, (const uint8_t *)t->flats, (const double *)t->mag, t->NN,
+                               save_cells, save_vals, nsave, cnt);
+            HIP_TRY(hipGetLastError());
+        }
+        size_t off = 0;
+        if (t->have[PYDEM_SECTION]) { kept.push_back({t->section, (size_t)t->NN, off}); off += (size_t)t->NN; }
+        if (t->have[PYDEM_EDGE_TODO]) { kept.push_back({t->edge_todo, (size_t)t->NN, off}); off += (size_t)t->NN; }
+        off = (off + 255) & ~(size_t)255;
+        if (t->have[PYDEM_PROPORTION]) { kept.push_back({t->prop, (size_t)t->NN * 8, off}); off += (size_t)t->NN * 8; }
+        if (off) HIP_TRY(dev_malloc(&planes.p, off));
+        for (const Kept &k : kept)
+            HIP_TRY(hipMemcpyAsync((char *)planes.p + k.off, k.dst, k.bytes, hipMemcpyDeviceToDevice, t->stream));
+        t->graph_valid = false;
+    }
+    int rc = own_graph ? ensure_graph(t, opt, "pydem_uca_weighted") : 0;
+    if (rc == 0) {
+        // (incremental edge rounds keep their state in the planes the sweep works in.  The upload of PYDEM_WEIGHT that every call
+        // needs has settled and dropped that state already; this is for a caller that reaches here otherwise)
+        if (t->einc_ready) rc = stage_edge_flush(t);
+        t->einc_ready = false;
+    }
+    if (rc == 0) rc = ensure_field(t, PYDEM_UCA_WEIGHTED);
+    if (rc == 0) rc = stage_uca_weighted(t, opt, scale_by_cell_area);
+    t->have[PYDEM_WEIGHT] = false;      // the plane holds the seeds now: the next call needs the weights again
+    const double w_ms = t->tm.uca_weighted_ms;
+    t->tm = keep;
+    if (rc == 0) t->tm.uca_weighted_ms = w_ms;
+    if (own_graph) {
+        if (nsave > 0) {
+            const int64_t g = cdiv(nsave, 256);
+            hipLaunchKernelGGL(k_flat_restore, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, t->stream, (const int32_t *)save_cells,
+                               (const double *)save_vals, nsave, t->mag, t->flats);
+        }
+        for (const Kept &k : kept)
+            HIP_TRY(hipMemcpyAsync(k.dst, (char *)planes.p + k.off, k.bytes, hipMemcpyDeviceToDevice, t->stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        t->graph_valid = false;
+    }
+    if (rc != 0) return rc;
+    t->have[PYDEM_UCA_WEIGHTED] = true;
     return 0;
 }
 

@@ -766,7 +766,9 @@ __device__ __forceinline__ void tile_stage(const SweepArgs &A, const TileBase &B
     }
 }
 
-template <bool LISTED>
+// WT (the weighted sweep, pydem_uca_weighted): A.a0 holds a seed per CELL instead of the cell area per row, and the shares are
+// summed with their signs -- a weight may be zero or negative, so the edge_todo taint cannot ride in the sign and is left out
+template <bool LISTED, bool WT = false>
 __device__ __forceinline__ void sweep_one_tile(const SweepArgs &A, TileW &L, uint32_t pass, int tiles_x, int tid, int lane,
                                                uint8_t *__restrict__ tile_done, int32_t &n_final, const TileNext &N,
                                                int32_t *pend, int &npend, const int32_t *nbr16)
@@ -790,7 +792,7 @@ __device__ __forceinline__ void sweep_one_tile(const SweepArgs &A, TileW &L, uin
     int nrounds = 0;
     if (prof) tk0 = wall_clock64();
     if (lane == 0) { L.tail = 0; L.limit = INT32_MAX; }
-    const double a0_row = (lane < TH && i0 + lane < n) ? A.a0[i0 + lane] : 0.0;       // lands in LDS once the final bitmap is no longer needed
+    const double a0_row = (!WT && lane < TH && i0 + lane < n) ? A.a0[i0 + lane] : 0.0;       // lands in LDS once the final bitmap is no longer needed
     constexpr int NSET = TH * TT / 64;
     tile_stage(A, B, L, pass, i0, j0, lane);
     tile_wave_sync();
@@ -908,20 +910,30 @@ __device__ __forceinline__ void sweep_one_tile(const SweepArgs &A, TileW &L, uin
                     if (d == cd) xs[q] = cv; else xs[q] = in_edge_h(B, nbr16, h, d);
                 }
             }
-            double a = L.a0[li - 1];
-            bool td = (gi == 0 || gi == n - 1 || gj == 0 || gj == m - 1) && ld_off<uint8_t>(B.todo, h) != 0;
+            double a;
+            bool td;
+            if constexpr (WT) {
+                a = A.a0[c];
+                td = false;
 #pragma unroll
-            for (int q = 0; q < 4; q++) { a += fabs(xs[q]); td = td || (xs[q] < 0); }       // (+0.0 leaves the positive sum as it is)
+                for (int q = 0; q < 4; q++) a += xs[q];
+            } else {
+                a = L.a0[li - 1];
+                td = (gi == 0 || gi == n - 1 || gj == 0 || gj == m - 1) && ld_off<uint8_t>(B.todo, h) != 0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) { a += fabs(xs[q]); td = td || (xs[q] < 0); }       // (+0.0 leaves the positive sum as it is)
+            }
             while (mm) {                                                                    // five and more in-edges: rare
                 const int d = __ffs(mm) - 1; mm &= mm - 1u;
                 const double x = (d == cd) ? cv : in_edge_h(B, nbr16, h, d);
-                a += fabs(x); td = td || (x < 0);
+                if constexpr (WT) a += x;
+                else { a += fabs(x); td = td || (x < 0); }
             }
             if (cw & CI_PIT_IN)
                 for (int32_t e = po.x; e < A.n_pit && A.pin_dst[e] == c; e++) {
                     const int32_t sc = A.pin_src[e];
                     a += A.area[sc] * A.pin_w[e];
-                    td = td || (A.todo_work[sc] != 0);
+                    if constexpr (!WT) td = td || (A.todo_work[sc] != 0);
                 }
             double2 o = make_double2(0.0, 0.0);
             if (cw & CI_OUT1) o.x = a * pv;
@@ -1025,7 +1037,7 @@ __device__ __forceinline__ void sweep_one_tile(const SweepArgs &A, TileW &L, uin
 #define PYDEM_FULL_WPB 4            // wavefronts per workgroup of the two full passes
 #endif
 constexpr int FWPB = PYDEM_FULL_WPB;
-template <bool LISTED>
+template <bool LISTED, bool WT = false>
 __global__ __launch_bounds__(64 * FWPB, 32 / FWPB) void k_sweep_tiles(SweepArgs A, uint32_t pass, int tiles_x, int tiles_total,
                                                      uint8_t *__restrict__ tile_done, int32_t *n_final, TileNext N, int32_t *work8)
 {
@@ -1051,7 +1063,7 @@ __global__ __launch_bounds__(64 * FWPB, 32 / FWPB) void k_sweep_tiles(SweepArgs 
     const int per4 = (gridDim.x >> 3) * 4;
     for (int tid = (blockIdx.x & 7) * per4 + (blockIdx.x >> 3) * 4 + wave, once = 0; once < 1; once++) {
         if (tid < tiles_total && !tile_done[tid])
-            sweep_one_tile<LISTED>(A, L[wave], pass, tiles_x, tid, lane, tile_done, fin, N, s_pend[wave], npend, s_nbr16);
+            sweep_one_tile<LISTED, WT>(A, L[wave], pass, tiles_x, tid, lane, tile_done, fin, N, s_pend[wave], npend, s_nbr16);
     }
 #else
     const int per = (tiles_total + 7) >> 3;
@@ -1065,7 +1077,7 @@ __global__ __launch_bounds__(64 * FWPB, 32 / FWPB) void k_sweep_tiles(SweepArgs 
             const int tid = xcd * per + q;
             if (q >= per || tid >= tiles_total) break;
             if (tile_done[tid]) continue;
-            sweep_one_tile<LISTED>(A, L[wave], pass, tiles_x, tid, lane, tile_done, fin, N, s_pend[wave], npend, s_nbr16);
+            sweep_one_tile<LISTED, WT>(A, L[wave], pass, tiles_x, tid, lane, tile_done, fin, N, s_pend[wave], npend, s_nbr16);
             if (LISTED && npend > TILE_PEND - 10) flush();      // (a visit adds at most ten)
         }
     }
@@ -1084,6 +1096,7 @@ __global__ __launch_bounds__(64 * FWPB, 32 / FWPB) void k_sweep_tiles(SweepArgs 
 #define PYDEM_LISTED_WPB 2          // wavefronts (= tiles in flight) per workgroup of the listed passes (same-box A/B: 4: 30.36, 1: 29.83, 2: 29.68 ms of sweep)
 #endif
 constexpr int LWPB = PYDEM_LISTED_WPB;
+template <bool WT = false>
 __global__ __launch_bounds__(64 * LWPB, PYDEM_LISTED_OCC) void k_sweep_tiles_listed(SweepArgs A, uint32_t pass, int tiles_x, const int32_t *__restrict__ list_in,
                                                             const int32_t *n_in, uint8_t *__restrict__ tile_done, int32_t *n_final,
                                                             TileNext N, int32_t *clear_count, int32_t *work3, SymArgs Y)
@@ -1134,8 +1147,8 @@ __global__ __launch_bounds__(64 * LWPB, PYDEM_LISTED_OCC) void k_sweep_tiles_lis
 #endif
         const int tid = __builtin_amdgcn_readfirstlane(list_in[k]);
         const uint32_t blk = Y.tile_sym ? __builtin_amdgcn_readfirstlane(Y.tile_sym[tid]) : SYM_NONE;
-        if (blk != SYM_NONE) sym_light_visit(A, Y, SL[wave], pass, tiles_x, tid, lane, blk, fin, N, s_pend[wave], npend);     // (a tile that went symbolic, K5f)
-        else sweep_one_tile<true>(A, L[wave], pass, tiles_x, tid, lane, tile_done, fin, N, s_pend[wave], npend, s_nbr16);
+        if (blk != SYM_NONE) sym_light_visit<WT>(A, Y, SL[wave], pass, tiles_x, tid, lane, blk, fin, N, s_pend[wave], npend);     // (a tile that went symbolic, K5f)
+        else sweep_one_tile<true, WT>(A, L[wave], pass, tiles_x, tid, lane, tile_done, fin, N, s_pend[wave], npend, s_nbr16);
         if (npend > TILE_PEND - 10) flush();            // (a visit adds at most ten)
     }
     if (npend) flush();
@@ -1245,6 +1258,7 @@ __device__ __forceinline__ int nb_local(int cell, int d)
     return cell + (di - 1) * TT + (q - 3 * di - 1);
 }
 
+template <bool WT = false>
 __device__ __forceinline__ void sweep_tile_resident(const SweepArgs &A, TileR &R, uint32_t pass, int tiles_x, int tid, int lane,
                                                     uint8_t *__restrict__ tile_done, int32_t &n_final, const TileNext &N,
                                                     int32_t *pend, int &npend)
@@ -1255,7 +1269,7 @@ __device__ __forceinline__ void sweep_tile_resident(const SweepArgs &A, TileR &R
     const int half = lane >> 5, l32 = lane & 31;
     constexpr int NSET = TH * TT / 64;
     if (lane == 0) L.tail = 0;
-    const double a0_row = (lane < TH && i0 + lane < n) ? A.a0[i0 + lane] : 0.0;
+    const double a0_row = (!WT && lane < TH && i0 + lane < n) ? A.a0[i0 + lane] : 0.0;
     tile_stage(A, tile_base(A, i0, j0), L, pass, i0, j0, lane);
     tile_wave_sync();
     // ---- setup: open-upstream counts (as in the generic visit) and a slot per open cell
@@ -1313,7 +1327,7 @@ __device__ __forceinline__ void sweep_tile_resident(const SweepArgs &A, TileR &R
         const uint32_t cw = L.cs[cell] >> 16;
         double pv = 0.0;
         if (cw & (CI_OUT1 | CI_OUT2)) pv = A.prop[c];
-        bool td = (gi == 0 || gi == n - 1 || gj == 0 || gj == m - 1) && A.todo_work[c] != 0;
+        bool td = !WT && (gi == 0 || gi == n - 1 || gj == 0 || gj == m - 1) && A.todo_work[c] != 0;
         uint32_t mm = (smv >> RS_FINAL_SHIFT) & 0xFFu;
         double xs[4];
 #pragma unroll
@@ -1321,10 +1335,18 @@ __device__ __forceinline__ void sweep_tile_resident(const SweepArgs &A, TileR &R
             xs[q] = 0.0;
             if (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; xs[q] = in_edge(A, c, m, d); }
         }
-        double K = L.a0[cell >> 5];
+        double K;
+        if constexpr (WT) {
+            K = A.a0[c];
 #pragma unroll
-        for (int q = 0; q < 4; q++) { K += fabs(xs[q]); td = td || (xs[q] < 0); }
-        while (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; const double x = in_edge(A, c, m, d); K += fabs(x); td = td || (x < 0); }
+            for (int q = 0; q < 4; q++) K += xs[q];
+            while (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; K += in_edge(A, c, m, d); }
+        } else {
+            K = L.a0[cell >> 5];
+#pragma unroll
+            for (int q = 0; q < 4; q++) { K += fabs(xs[q]); td = td || (xs[q] < 0); }
+            while (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; const double x = in_edge(A, c, m, d); K += fabs(x); td = td || (x < 0); }
+        }
         R.Kd[s] = K; R.Pd[s] = pv;
         R.sm[s] = (smv & RS_CELL_OPEN) | (td ? RS_TAINT : 0u);
     }
@@ -1363,7 +1385,7 @@ __device__ __forceinline__ void sweep_tile_resident(const SweepArgs &A, TileR &R
                     bool here = false;
                     if (si >= 0 && si < TH && sj >= 0 && sj < TT) here = sp_state(L, si * TT + sj) == 2u;      // finished in this visit
                     if (here) { const int ss = R.map[si * TT + sj]; a += R.Kd[ss] * A.pin_w[e]; td = td || (R.sm[ss] & RS_TAINT); }
-                    else { a += A.area[sc] * A.pin_w[e]; td = td || (A.todo_work[sc] != 0); }
+                    else { a += A.area[sc] * A.pin_w[e]; if constexpr (!WT) td = td || (A.todo_work[sc] != 0); }
                 }
             R.Kd[s] = a;
             R.sm[s] = (smv & RS_CELL) | (td ? RS_TAINT : 0u) | RS_FIN;
@@ -1428,6 +1450,7 @@ __device__ __forceinline__ void sweep_tile_resident(const SweepArgs &A, TileR &R
 }
 
 // listed passes with few tiles: one wavefront (= one workgroup) per tile, resident visit when the tile's open cells fit
+template <bool WT = false>
 __global__ __launch_bounds__(64) void k_sweep_tiles_resident(SweepArgs A, uint32_t pass, int tiles_x, const int32_t *__restrict__ list_in,
                                                              const int32_t *n_in, uint8_t *__restrict__ tile_done, int32_t *n_final,
                                                              TileNext N, int32_t *clear_count, SymArgs Y)
@@ -1455,11 +1478,11 @@ __global__ __launch_bounds__(64) void k_sweep_tiles_resident(SweepArgs A, uint32
     for (int32_t k = blockIdx.x; k < nt; k += gridDim.x) {
         const int tid = __builtin_amdgcn_readfirstlane(list_in[k]);
         const uint32_t blk = Y.tile_sym ? __builtin_amdgcn_readfirstlane(Y.tile_sym[tid]) : SYM_NONE;
-        if (blk != SYM_NONE) sym_light_visit(A, Y, SL, pass, tiles_x, tid, lane, blk, fin, N, s_pend, npend);
+        if (blk != SYM_NONE) sym_light_visit<WT>(A, Y, SL, pass, tiles_x, tid, lane, blk, fin, N, s_pend, npend);
         else if (__builtin_amdgcn_readfirstlane(A.tile_open[tid]) <= RCAP)
-            sweep_tile_resident(A, R, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend);
+            sweep_tile_resident<WT>(A, R, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend);
         else
-            sweep_one_tile<true>(A, R.W, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend, s_nbr16);
+            sweep_one_tile<true, WT>(A, R.W, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend, s_nbr16);
         if (npend > TILE_PEND - 10) flush();
     }
     if (npend) flush();
@@ -1679,6 +1702,36 @@ __global__ void k_row_area(const double *__restrict__ dX2, const double *__restr
     if (i < n) a0[i] = dX2[i] * dY2[i];                                          // :885
 }
 
+// ------------------------------------------------------------------------------- K5w
+// Weighted sweep (pydem_uca_weighted): the same schedule from a per-cell seed.  _calc_uca_chunk starts its sweep from
+// area = dX2 * dY2 per row (dem_processing.py:885, :901) and cyutils.pyx:163 is linear in it, so a weighted accumulation
+// is that sweep started from w * dX2 * dY2 (or w).  The seed is formed once, in place in the weight plane: w[c] * a0[i]
+// is what the plain sweep's a0[i] is for w = 1, so the two agree bit for bit there.
+__global__ void k_weight_seed(const double *__restrict__ dX2, const double *__restrict__ dY2, int n, int m, double *__restrict__ w)
+{
+    for (int i = blockIdx.y; i < n; i += gridDim.y) {
+        const double a0 = dX2[i] * dY2[i];                                        // :885 (k_row_area)
+        for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) w[(int64_t)i * m + j] *= a0;
+    }
+}
+
+// the level field of every graph word as the graph stage leaves it (sources 0, every other cell "not yet known"): a
+// sweep consumes the stamps, an edge round keeps its counts there
+__global__ void k_sweep_rearm(uint32_t *__restrict__ cinfo, int64_t NN)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < NN; c += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t w = cinfo[c] & CI_STATIC_MASK;
+        cinfo[c] = w | (((w & (0xFFu | CI_PIT_IN)) ? CI_LEVEL_INF : 0u) << CI_LEVEL_SHIFT);
+    }
+}
+
+// :972 only (no edge masks: the weighted call leaves edge_todo / edge_done alone)
+__global__ void k_uca_weighted_finalize(double *__restrict__ uca_w, const uint8_t *__restrict__ flats, int64_t NN)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < NN; c += (int64_t)gridDim.x * blockDim.x)
+        if (flats[c]) uca_w[c] = NAN;
+}
+
 // ------------------------------------------------------------------------------- K5c
 // Circular drainage (rare: e.g. the overlap-1 patch of a tile's edge aspects can close a two-cell loop).  When the tile
 // passes stall, the cells on and below the loop are unfinished; the reference then re-seeds its push sweep from the
@@ -1693,25 +1746,28 @@ struct ReseedCell { int32_t c; int32_t pin_first; int32_t pout_first; int32_t pa
 __device__ __forceinline__ bool ci_unfinished(uint32_t w) { const uint32_t lv = ci_level(w); return lv == 0 || lv == CI_LEVEL_INF; }
 
 // area / taint an unfinished cell has received so far: the shares of its FINISHED upstream cells (graph word level >= 1)
+// (WT: seed per cell, signed shares, no taint -- see sweep_one_tile)
+template <bool WT = false>
 __device__ void gather_finished(const SweepArgs &A, int32_t c, uint32_t cw, int32_t pin_first, double &a, bool &td)
 {
     const int m = A.m, gi = c / m, gj = c - gi * m;
-    a = A.a0[gi];
-    td = (gi == 0 || gi == A.n - 1 || gj == 0 || gj == m - 1) && A.todo_work[c] != 0;
+    a = WT ? A.a0[c] : A.a0[gi];
+    td = !WT && (gi == 0 || gi == A.n - 1 || gj == 0 || gj == m - 1) && A.todo_work[c] != 0;
     for (int d = 0; d < 8; d++)
         if (cw & (1u << d)) {
             const int32_t u = c + NB_DI[d] * m + NB_DJ[d];
             if (ci_unfinished(A.cinfo[u])) continue;
             const bool cardinal = (NB_DI[d] == 0) || (NB_DJ[d] == 0);
             const double x = cardinal ? A.contrib[u].x : A.contrib[u].y;
-            a += fabs(x); td = td || (x < 0);
+            if constexpr (WT) a += x;
+            else { a += fabs(x); td = td || (x < 0); }
         }
     if (cw & CI_PIT_IN)
         for (int32_t e = pin_first; e < A.n_pit && A.pin_dst[e] == c; e++) {
             const int32_t sc = A.pin_src[e];
             if (ci_unfinished(A.cinfo[sc])) continue;
             a += A.area[sc] * A.pin_w[e];
-            td = td || (A.todo_work[sc] != 0);
+            if constexpr (!WT) td = td || (A.todo_work[sc] != 0);
         }
 }
 
@@ -1741,6 +1797,7 @@ __device__ __forceinline__ int reseed_find(const ReseedCell *U, int32_t nU, int3
 }
 
 // ONE thread.  st[k]: bit 0 done, bit 1 in the current frontier, bit 2 in the previous frontier; tdf[k]: taint
+template <bool WT = false>
 __global__ void k_reseed_replay(SweepArgs A, const ReseedCell *__restrict__ U, int32_t nU, const double *__restrict__ elev,
                                 const double *__restrict__ pit_w, uint8_t *__restrict__ st, uint8_t *__restrict__ tdf,
                                 int tile_has_nan, int maxcount, uint32_t pass, int32_t *n_final, int32_t *n_done_out)
@@ -1756,7 +1813,7 @@ __global__ void k_reseed_replay(SweepArgs A, const ReseedCell *__restrict__ U, i
     // what the unfinished cells have received so far
     for (int k = 0; k < nU; k++) {
         double a; bool td;
-        gather_finished(A, U[k].c, A.cinfo[U[k].c] & CI_STATIC_MASK, U[k].pin_first, a, td);
+        gather_finished<WT>(A, U[k].c, A.cinfo[U[k].c] & CI_STATIC_MASK, U[k].pin_first, a, td);
         A.area[U[k].c] = a; tdf[k] = td; st[k] = 0;
     }
     int32_t n_done = 0, done_prev = -1;
@@ -1827,6 +1884,7 @@ __global__ void k_reseed_replay(SweepArgs A, const ReseedCell *__restrict__ U, i
 // cell -- its static graph word, elevation, proportion, pit-list offsets and what it has received from its finished
 // upstream cells -- gathered in parallel; the results come back through k_reseed_scatter.
 struct ReseedHost { int32_t c; uint32_t cw; int32_t pin_first, pout_first; double area, elev, prop; int32_t td, pad; };
+template <bool WT = false>
 __global__ __launch_bounds__(256) void k_reseed_gather(SweepArgs A, const ReseedCell *__restrict__ U, int32_t nU, const double *__restrict__ elev,
                                                        ReseedHost *__restrict__ out)
 {
@@ -1834,7 +1892,7 @@ __global__ __launch_bounds__(256) void k_reseed_gather(SweepArgs A, const Reseed
         ReseedHost h;
         h.c = U[k].c; h.cw = A.cinfo[h.c] & CI_STATIC_MASK; h.pin_first = U[k].pin_first; h.pout_first = U[k].pout_first;
         double a; bool td;
-        gather_finished(A, h.c, h.cw, h.pin_first, a, td);
+        gather_finished<WT>(A, h.c, h.cw, h.pin_first, a, td);
         h.area = a; h.td = td; h.pad = 0; h.elev = elev[h.c]; h.prop = (h.cw & (CI_OUT1 | CI_OUT2)) ? A.prop[h.c] : 0.0;
         out[k] = h;
     }
@@ -2901,6 +2959,7 @@ int grid_for(int64_t work, int cap) { const int64_t g = cdiv(work, 256); return 
 int stage_section_graph(pydem_tile *t, const pydem_options *opt)
 {
     const int n = (int)t->n, m = (int)t->m;
+    t->graph_opt = *opt;
     t->edge_clean = false;
     t->einc_ready = false;
     PYDEM_TRY(tile_alloc(t, &t->todo_work, (size_t)t->NN));
@@ -3036,7 +3095,11 @@ static int64_t reseed_replay_host(std::vector<ReseedHost> &H, std::vector<uint8_
     return n_done;
 }
 
-int stage_sweep(pydem_tile *t, const pydem_options *opt)
+// The sweep schedule.  WT = false: pydem_uca's sweep into t->uca (fill_sweep_args).  WT = true: the weighted sweep of
+// pydem_uca_weighted -- A.a0 = the per-cell seeds, A.area = t->uca_w, the same schedule (dense / LDS first-pass diagnostics
+// and the queue schedule are not offered), NaN on flats only, no edge masks.
+template <bool WT>
+static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
 {
     const int n = (int)t->n, m = (int)t->m;
     // (the tile visits address a tile + halo by 32-bit byte offsets from a scalar base: 34 rows of 16-byte entries)
@@ -3054,11 +3117,12 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
 #endif
     HIP_TRY(hipEventRecord(t->ev[0], t->stream));
     HIP_TRY(hipMemsetAsync(t->counters, 0, 16 * sizeof(int32_t), t->stream));
-    hipLaunchKernelGGL(k_row_area, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, t->stream, t->dX2, t->dY2, n, t->row_area);
+    if (!WT) hipLaunchKernelGGL(k_row_area, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, t->stream, t->dX2, t->dY2, n, t->row_area);
     SweepArgs A;
     fill_sweep_args(t, A);
+    if (WT) { A.a0 = seed; A.area = t->uca_w; }
     if (A.n_pit > 0)   // the unused area slots of pit sources / drains carry their edge-list offsets until they are processed
-        hipLaunchKernelGGL(k_pit_stash, dim3(grid_for(A.n_pit, 2048)), dim3(256), 0, t->stream, A.pin_dst, A.pit_src, A.n_pit, t->uca);
+        hipLaunchKernelGGL(k_pit_stash, dim3(grid_for(A.n_pit, 2048)), dim3(256), 0, t->stream, A.pin_dst, A.pit_src, A.n_pit, A.area);
     // ---- tile-local passes until they stop paying, then the queue rounds take over
     const int tiles_x = (int)cdiv(m, TT), tiles_total = tiles_x * (int)cdiv(n, TH);
     // scratch: tile_done bytes | per-tile "listed for pass" stamps | two tile lists | open cells per tile
@@ -3123,11 +3187,11 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
             for (int b = 0; b < batch; b++, p++) {
                 N.list = tile_list[(p + 1) % 2]; N.count = &cntT[(p + 1) % 3];
                 if (resident)
-                    hipLaunchKernelGGL(k_sweep_tiles_resident, dim3((unsigned)(ntiles > 256 ? ntiles : 256)), dim3(64), 0, t->stream, A, (uint32_t)p, tiles_x,
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_tiles_resident<WT>), dim3((unsigned)(ntiles > 256 ? ntiles : 256)), dim3(64), 0, t->stream, A, (uint32_t)p, tiles_x,
                                        (const int32_t *)tile_list[p % 2], (const int32_t *)&cntT[p % 3], tile_done, total, N,
                                        &cntT[(p + 2) % 3], Y);
                 else
-                    hipLaunchKernelGGL(k_sweep_tiles_listed, dim3(grid), dim3(64 * LWPB), (size_t)lds_pad, t->stream, A, (uint32_t)p, tiles_x,
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_tiles_listed<WT>), dim3(grid), dim3(64 * LWPB), (size_t)lds_pad, t->stream, A, (uint32_t)p, tiles_x,
                                        (const int32_t *)tile_list[p % 2], (const int32_t *)&cntT[p % 3], tile_done, total, N,
                                        &cntT[(p + 2) % 3], work3, Y);
                 launches++;
@@ -3181,7 +3245,7 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
                 ReseedHost *dH = (ReseedHost *)((char *)d_tmp + (size_t)nU * sizeof(ReseedCell));
                 HIP_TRY(hipMemsetAsync(rc, 0, 3 * sizeof(int32_t), t->stream));
                 hipLaunchKernelGGL(k_reseed_collect, dim3(grid_for(t->NN, 4096)), dim3(256), 0, t->stream, A, U2, rc, nU, (const double *)t->elev, rc + 1);
-                hipLaunchKernelGGL(k_reseed_gather, dim3(grid_for(nU, 1024)), dim3(256), 0, t->stream, A, (const ReseedCell *)U2, nU, (const double *)t->elev, dH);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reseed_gather<WT>), dim3(grid_for(nU, 1024)), dim3(256), 0, t->stream, A, (const ReseedCell *)U2, nU, (const double *)t->elev, dH);
                 std::vector<ReseedHost> H((size_t)nU);
                 HIP_TRY(hipMemcpyAsync(H.data(), dH, (size_t)nU * sizeof(ReseedHost), hipMemcpyDeviceToHost, t->stream));
                 HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, 64 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
@@ -3216,7 +3280,7 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
             HIP_TRY(hipStreamSynchronize(t->stream));
             std::sort(hu.begin(), hu.end(), [](const ReseedCell &a, const ReseedCell &b) { return a.c < b.c; });
             HIP_TRY(hipMemcpyAsync(U, hu.data(), hu.size() * sizeof(ReseedCell), hipMemcpyHostToDevice, t->stream));
-            hipLaunchKernelGGL(k_reseed_replay, dim3(1), dim3(64), 0, t->stream, A, (const ReseedCell *)U, (int32_t)unfinished,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reseed_replay<WT>), dim3(1), dim3(64), 0, t->stream, A, (const ReseedCell *)U, (int32_t)unfinished,
                                (const double *)t->elev, (const double *)t->pits.w, stf, stf + unfinished, t->h_counters[61],
                                (int)opt->circular_ref_maxcount, pass, total, rc + 2);
             launches += 2;
@@ -3232,6 +3296,7 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
 #ifdef PYDEM_SWEEP_QUEUE
     static int sweep_mode = -1;
     if (sweep_mode < 0) { const char *e = getenv("PYDEM_SWEEP_MODE"); sweep_mode = (e && !strcmp(e, "queue")) ? 1 : 0; }
+    if (WT && sweep_mode == 1) { pydem_set_error("pydem_uca_weighted: PYDEM_SWEEP_MODE=queue is not supported (the weighted sweep runs the tile passes)"); return -6; }
 #else
     constexpr int sweep_mode = 0;
 #endif
@@ -3253,20 +3318,20 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
         // the default (profiles/r04_sweep_passes_dense*.txt)
         static int dense_levels = -1;
         if (dense_levels < 0) { const char *e = getenv("PYDEM_SWEEP_DENSE"); dense_levels = e ? atoi(e) : 0; if (dense_levels < 0) dense_levels = 0; }
-        for (int lv = 1; lv <= dense_levels; lv++) {
+        for (int lv = 1; !WT && lv <= dense_levels; lv++) {
             hipLaunchKernelGGL(k_sweep_dense_level, dim3((unsigned)cdiv(m, 256), (unsigned)cdiv(n, DENSE_BAND)), dim3(256), 0, t->stream,
                                A, (uint32_t)lv, total);
             launches++;
         }
-        const uint32_t pb = (uint32_t)dense_levels;       // passes so far
-        if (first_kind == 1 && TH == 32 && pb == 0)
+        const uint32_t pb = WT ? 0u : (uint32_t)dense_levels;       // passes so far
+        if (!WT && first_kind == 1 && TH == 32 && pb == 0)
             hipLaunchKernelGGL(k_sweep_first, dim3((unsigned)(((tiles_total + 7) / 8) * 8)), dim3(256), 0, t->stream, A, tiles_x, tiles_total, tile_done, total);
         else {
             TileNext N0; N0.flag = nullptr; N0.list = nullptr; N0.count = nullptr;
-            hipLaunchKernelGGL(k_sweep_tiles<false>, dim3(full_grid), dim3(64 * FWPB), (size_t)lds_pad, t->stream, A, pb + 1u, tiles_x, tiles_total, tile_done, total, N0, work16);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_tiles<false, WT>), dim3(full_grid), dim3(64 * FWPB), (size_t)lds_pad, t->stream, A, pb + 1u, tiles_x, tiles_total, tile_done, total, N0, work16);
         }
         TileNext N; N.flag = tile_flag; N.list = tile_list[(pb + 3) % 2]; N.count = &cntT[(pb + 3) % 3];
-        hipLaunchKernelGGL(k_sweep_tiles<true>, dim3(full_grid), dim3(64 * FWPB), (size_t)lds_pad, t->stream, A, pb + 2u, tiles_x, tiles_total, tile_done, total, N, work16 + 8);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_tiles<true, WT>), dim3(full_grid), dim3(64 * FWPB), (size_t)lds_pad, t->stream, A, pb + 2u, tiles_x, tiles_total, tile_done, total, N, work16 + 8);
         HIP_TRY(hipMemsetAsync(work3, 0, 24 * sizeof(int32_t), t->stream));       // (the listed passes reuse the band counters' words: 3 x 8, rotating)
         launches += 2;
         HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, 64 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
@@ -3284,8 +3349,8 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
             // the three size classes side by side (each kernel lasts as long as its longest visits: 0.7 + 0.4 + 0.4 ms one after the other)
             HIP_TRY(hipEventRecord(t->ev_fork, t->stream));
             HIP_TRY(hipStreamWaitEvent(t->stream2, t->ev_fork, 0));
-            hipLaunchKernelGGL(k_sweep_sym<256>, dim3(256 * 32), dim3(64), 0, t->stream, A, Y, ps, tiles_x, tiles_total, tile_done, total, N3, (const int32_t *)cand, (const int32_t *)(symc + 16), 0, 0);
-            hipLaunchKernelGGL(k_sweep_sym<1024>, dim3(256 * 16), dim3(64), 0, t->stream2, A, Y, ps, tiles_x, tiles_total, tile_done, total, N3, (const int32_t *)cand, (const int32_t *)(symc + 17), 1, 256);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_sym<256, WT>), dim3(256 * 32), dim3(64), 0, t->stream, A, Y, ps, tiles_x, tiles_total, tile_done, total, N3, (const int32_t *)cand, (const int32_t *)(symc + 16), 0, 0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_sym<1024, WT>), dim3(256 * 16), dim3(64), 0, t->stream2, A, Y, ps, tiles_x, tiles_total, tile_done, total, N3, (const int32_t *)cand, (const int32_t *)(symc + 17), 1, 256);
             HIP_TRY(hipEventRecord(t->ev_join, t->stream2));
             HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0));
             launches += 4;
@@ -3300,7 +3365,7 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
         t->tm.sweep_tile_passes = (int64_t)pass;
         if (sym_on) {
             // K5f (c): the cells that still carry a symbolic header
-            hipLaunchKernelGGL(k_sym_finish, dim3((unsigned)std::min<int64_t>(tiles_total, 256 * 16)), dim3(64), 0, t->stream, A, Y, pass, tiles_x, tiles_total, total);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sym_finish<WT>), dim3((unsigned)std::min<int64_t>(tiles_total, 256 * 16)), dim3(64), 0, t->stream, A, Y, pass, tiles_x, tiles_total, total);
             launches++;
             if (getenv("PYDEM_SWEEP_DEBUG")) {
                 int32_t hs[64];
@@ -3439,10 +3504,14 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
     const int64_t processed = (int64_t)t->h_counters[3];     // tile passes + queue rounds ([4], [10]: tile-pass statistics)
     t->tm.n_unresolved = t->NN - processed;
     t->tm.sweep_kernel_launches = launches;
-    double min_area = INFINITY;
-    for (int64_t i = 0; i < t->n; i++) { const double a = t->h_dX2[(size_t)i] * t->h_dY2[(size_t)i]; if (a < min_area) min_area = a; }
-    hipLaunchKernelGGL(k_uca_finalize, dim3(grid_for(t->NN, 8192)), dim3(256), 0, t->stream, t->uca, t->flats, t->todo_work,
-                       t->elev, t->edge_done, t->NN, opt->apply_uca_limit_edges, opt->uca_saturation_limit * 2 * min_area);
+    if (WT) {
+        hipLaunchKernelGGL(k_uca_weighted_finalize, dim3(grid_for(t->NN, 8192)), dim3(256), 0, t->stream, t->uca_w, (const uint8_t *)t->flats, t->NN);
+    } else {
+        double min_area = INFINITY;
+        for (int64_t i = 0; i < t->n; i++) { const double a = t->h_dX2[(size_t)i] * t->h_dY2[(size_t)i]; if (a < min_area) min_area = a; }
+        hipLaunchKernelGGL(k_uca_finalize, dim3(grid_for(t->NN, 8192)), dim3(256), 0, t->stream, t->uca, t->flats, t->todo_work,
+                           t->elev, t->edge_done, t->NN, opt->apply_uca_limit_edges, opt->uca_saturation_limit * 2 * min_area);
+    }
     HIP_TRY(hipEventRecord(t->ev[1], t->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventSynchronize(t->ev[1]));
@@ -3451,6 +3520,33 @@ int stage_sweep(pydem_tile *t, const pydem_options *opt)
     t->tm.sweep_ms = ms;
     t->tm.sweep_rounds = t->h_counters[5];
     return 0;
+}
+
+int stage_sweep(pydem_tile *t, const pydem_options *opt) { return sweep_schedule<false>(t, opt, nullptr); }
+
+// pydem_uca_weighted on the tile's flow graph: the seed in place in the weight plane, the level stamps re-armed, the weighted
+// schedule.  The sweep's work state -- level stamps, contribution records, queue buffers, scratch -- is shared with the plain
+// path; every timing and counter of the plain path is put back, and the next edge round rebuilds its state (edge_clean).
+int stage_uca_weighted(pydem_tile *t, const pydem_options *opt, int scale_by_cell_area)
+{
+    const int n = (int)t->n, m = (int)t->m;
+    HIP_TRY(hipEventRecord(t->ev[2], t->stream));
+    t->edge_clean = false;              // the level fields and the contribution records carried the classic rounds' state
+    if (scale_by_cell_area) {
+        const dim3 grid2((unsigned)(cdiv(m, 256) < 64 ? cdiv(m, 256) : 64), (unsigned)(n < 16384 ? n : 16384));
+        hipLaunchKernelGGL(k_weight_seed, grid2, dim3(256), 0, t->stream, (const double *)t->dX2, (const double *)t->dY2, n, m, t->weight);
+    }
+    hipLaunchKernelGGL(k_sweep_rearm, dim3(grid_for(t->NN, 8192)), dim3(256), 0, t->stream, (uint32_t *)t->indeg, t->NN);
+    HIP_TRY(hipGetLastError());
+    const pydem_timings keep = t->tm;
+    const int64_t keep_circular = t->circular_cells;
+    const int rc = sweep_schedule<true>(t, opt, t->weight);
+    float ms = 0;
+    if (rc == 0) HIP_TRY(hipEventElapsedTime(&ms, t->ev[2], t->ev[1]));      // seed + re-arm + schedule (ev[1]: end of the schedule, synchronised)
+    t->tm = keep;
+    t->circular_cells = keep_circular;
+    if (rc == 0) t->tm.uca_weighted_ms = ms;
+    return rc;
 }
 
 int stage_twi(pydem_tile *t, const pydem_options *opt)

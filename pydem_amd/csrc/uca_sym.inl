@@ -145,7 +145,8 @@ __device__ __forceinline__ int sym_nb_local(int cell, int d)
 
 // ONE symbolic visit (see the head of the file).  Returns false when the tile does not fit (inlets, slots, outlets, pool):
 // nothing but unused pool space has been written then, and the caller runs the numeric visit of this pass instead.
-template <int RC>
+// (WT: the weighted sweep -- seed per cell, signed shares, no taint; see sweep_one_tile)
+template <int RC, bool WT = false>
 __device__ bool sym_visit(const SweepArgs &A, const SymArgs &Y, SymAlloc &AL, TileS<RC> &S, uint32_t pass, int tiles_x, int tid, int lane,
                           uint8_t *__restrict__ tile_done, int32_t &n_final, const TileNext &N, int32_t *pend, int &npend)
 {
@@ -163,7 +164,7 @@ __device__ bool sym_visit(const SweepArgs &A, const SymArgs &Y, SymAlloc &AL, Ti
 #else
 #define SYM_TICK(i)
 #endif
-    const double a0_row = (lane < TH && i0 + lane < n) ? A.a0[i0 + lane] : 0.0;
+    const double a0_row = (!WT && lane < TH && i0 + lane < n) ? A.a0[i0 + lane] : 0.0;
     tile_stage(A, tile_base(A, i0, j0), L, pass, i0, j0, lane, S.hw);
     tile_wave_sync();
     SYM_TICK(1);
@@ -238,7 +239,7 @@ __device__ bool sym_visit(const SweepArgs &A, const SymArgs &Y, SymAlloc &AL, Ti
         const uint32_t cw = L.cs[cell] >> 16;
         double pv = 0.0;
         if (cw & (CI_OUT1 | CI_OUT2)) pv = A.prop[c];
-        bool td = (gi == 0 || gi == n - 1 || gj == 0 || gj == m - 1) && A.todo_work[c] != 0;
+        bool td = !WT && (gi == 0 || gi == n - 1 || gj == 0 || gj == m - 1) && A.todo_work[c] != 0;
         uint32_t mm = (smv >> SS_FINAL_SHIFT) & 0xFFu;
         double xs[4];
 #pragma unroll
@@ -246,10 +247,18 @@ __device__ bool sym_visit(const SweepArgs &A, const SymArgs &Y, SymAlloc &AL, Ti
             xs[q] = 0.0;
             if (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; xs[q] = in_edge(A, c, m, d); }
         }
-        double K = L.a0[cell >> 5];
+        double K;
+        if constexpr (WT) {
+            K = A.a0[c];
 #pragma unroll
-        for (int q = 0; q < 4; q++) { K += fabs(xs[q]); td = td || (xs[q] < 0); }
-        while (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; const double x = in_edge(A, c, m, d); K += fabs(x); td = td || (x < 0); }
+            for (int q = 0; q < 4; q++) K += xs[q];
+            while (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; K += in_edge(A, c, m, d); }
+        } else {
+            K = L.a0[cell >> 5];
+#pragma unroll
+            for (int q = 0; q < 4; q++) { K += fabs(xs[q]); td = td || (xs[q] < 0); }
+            while (mm) { const int d = __ffs(mm) - 1; mm &= mm - 1u; const double x = in_edge(A, c, m, d); K += fabs(x); td = td || (x < 0); }
+        }
         S.Kd[s] = K; S.Pd[s] = pv; S.mk[s] = 0ull; S.off[s] = 0u;
         S.sm[s] = (smv & (SS_CELL | (0xFFu << SS_OPEN_SHIFT))) | (td ? SS_TAINT : 0u);
         S.pe_n[s] = 0; S.po_n[s] = 0;
@@ -277,7 +286,7 @@ __device__ bool sym_visit(const SweepArgs &A, const SymArgs &Y, SymAlloc &AL, Ti
                 if (inside) { open_src = sp_state(L, si * TT + sj) == 0u; if (open_src) cnt++; }
                 else { const uint32_t lv = ci_level(A.cinfo[sc]); open_src = !(lv >= 1 && lv < pass); }
                 if (open_src) ne++;
-                else { kadd += A.area[sc] * A.pin_w[e]; td = td || (A.todo_work[sc] != 0); }
+                else { kadd += A.area[sc] * A.pin_w[e]; if constexpr (!WT) td = td || (A.todo_work[sc] != 0); }
             }
             int base = 0;
             if (ne) {
@@ -606,6 +615,8 @@ __device__ bool sym_visit(const SweepArgs &A, const SymArgs &Y, SymAlloc &AL, Ti
 struct SymLight { double x[SYM_MAXIN]; uint8_t t[SYM_MAXIN]; };
 
 // the inlets of a block that are final for a visit of pass `pass` (bit j of the result), their areas / taints into LDS
+// (WT: areas only)
+template <bool WT = false>
 __device__ __forceinline__ unsigned long long sym_load_inlets(const SweepArgs &A, const double *B, int J, SymLight &S, uint32_t pass, int lane)
 {
     const int32_t *ids = reinterpret_cast<const int32_t *>(B + 2);
@@ -614,13 +625,14 @@ __device__ __forceinline__ unsigned long long sym_load_inlets(const SweepArgs &A
         const int32_t u = ids[lane];
         const uint32_t lv = ci_level(A.cinfo[u]);
         fin = lv >= 1 && lv < pass;
-        if (fin) { S.x[lane] = A.area[u]; S.t[lane] = A.todo_work[u]; }
+        if (fin) { S.x[lane] = A.area[u]; if constexpr (!WT) S.t[lane] = A.todo_work[u]; }
     }
     return __ballot(fin);
 }
 
 // (b) light visit of a symbolic tile: every outlet all of whose inlets are final by now is evaluated and written like a
 // finished cell; the tiles it drains into are listed for the next pass
+template <bool WT = false>
 __device__ __forceinline__ void sym_light_visit(const SweepArgs &A, const SymArgs &Y, SymLight &S, uint32_t pass, int tiles_x, int tid, int lane,
                                                 uint32_t blk, int32_t &n_final, const TileNext &N, int32_t *pend, int &npend)
 {
@@ -628,7 +640,7 @@ __device__ __forceinline__ void sym_light_visit(const SweepArgs &A, const SymArg
     const unsigned long long h0 = (unsigned long long)__double_as_longlong(B[0]);
     const int J = (int)(h0 & 0xFFull), O = (int)((h0 >> 8) & 0xFFull);
     const unsigned long long res = (unsigned long long)__double_as_longlong(B[1]);
-    const unsigned long long F = sym_load_inlets(A, B, J, S, pass, lane);
+    const unsigned long long F = sym_load_inlets<WT>(A, B, J, S, pass, lane);
     tile_wave_sync();
     const double *R = B + 2 + (J + 1) / 2;
     const int by = tid / tiles_x, bx = tid - by * tiles_x;
@@ -647,7 +659,7 @@ __device__ __forceinline__ void sym_light_visit(const SweepArgs &A, const SymArg
             for (int k = 1; mask; k++) {
                 const int j = __ffsll((long long)mask) - 1; mask &= mask - 1ull;
                 a += E[k] * S.x[j];
-                td = td || (S.t[j] != 0);
+                if constexpr (!WT) td = td || (S.t[j] != 0);
             }
             const int cell = (int)(r0 & 0x3FFull);
             const int32_t c = (i0 + (cell >> 5)) * m + j0 + (cell & 31);
@@ -706,7 +718,7 @@ __global__ __launch_bounds__(256) void k_sym_candidates(const uint8_t *__restric
 // (a) the symbolic pass over one class of the unfinished tiles (k_sym_candidates): symbolic visit when the tile's open
 // cells fit the slots of this instantiation (lo < open cells <= RC; 1024 slots hold any tile), the numeric visit of this pass
 // for a tile whose symbolic visit gave up (inlets, outlets, pool).  One wavefront per workgroup, the list entries strided over the workgroups.
-template <int RC>
+template <int RC, bool WT = false>
 __global__ __launch_bounds__(64) void k_sweep_sym(SweepArgs A, SymArgs Y, uint32_t pass, int tiles_x, int tiles_total, uint8_t *__restrict__ tile_done,
                                                   int32_t *n_final, TileNext N, const int32_t *__restrict__ list, const int32_t *cnt, int from_back, int lo)
 {
@@ -734,11 +746,11 @@ __global__ __launch_bounds__(64) void k_sweep_sym(SweepArgs A, SymArgs Y, uint32
         const int tid = __builtin_amdgcn_readfirstlane(list[from_back ? tiles_total - 1 - k : k]);
         const int open = __builtin_amdgcn_readfirstlane(A.tile_open[tid]);
         if (open <= lo || open > RC) continue;              // (another instantiation's tile)
-        const bool numeric = !sym_visit<RC>(A, Y, AL, S, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend);
+        const bool numeric = !sym_visit<RC, WT>(A, Y, AL, S, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend);
         if (numeric) {
             if (lane == 0) atomicAdd(&Y.stat[1], 1);
             tile_wave_sync();
-            sweep_one_tile<true>(A, S.W, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend, s_nbr16);
+            sweep_one_tile<true, WT>(A, S.W, pass, tiles_x, tid, lane, tile_done, fin, N, s_pend, npend, s_nbr16);
         }
         if (npend > TILE_PEND - 10) flush();
     }
@@ -748,6 +760,7 @@ __global__ __launch_bounds__(64) void k_sweep_sym(SweepArgs A, SymArgs Y, uint32
 
 // (c) after the last pass: every cell that still carries a symbolic header is evaluated (all inlets final) or, below a
 // drainage loop, handed back to the unfinished cells (level "not yet known": the re-seed replay K5c reads that)
+template <bool WT = false>
 __global__ __launch_bounds__(64) void k_sym_finish(SweepArgs A, SymArgs Y, uint32_t pass, int tiles_x, int tiles_total, int32_t *n_final)
 {
     __shared__ SymLight S;
@@ -759,7 +772,7 @@ __global__ __launch_bounds__(64) void k_sym_finish(SweepArgs A, SymArgs Y, uint3
         if (blk == SYM_NONE) continue;
         const double *B = sym_ptr(Y, blk);
         const int J = (int)((unsigned long long)__double_as_longlong(B[0]) & 0xFFull);
-        const unsigned long long F = sym_load_inlets(A, B, J, S, pass, lane);
+        const unsigned long long F = sym_load_inlets<WT>(A, B, J, S, pass, lane);
         tile_wave_sync();
         const int by = tid / tiles_x, bx = tid - by * tiles_x;
         const int i0 = by * TH, j0 = bx * TT;
@@ -788,7 +801,7 @@ __global__ __launch_bounds__(64) void k_sym_finish(SweepArgs A, SymArgs Y, uint3
                 for (int q = 1; mask; q++) {
                     const int j = __ffsll((long long)mask) - 1; mask &= mask - 1ull;
                     a += E[q] * S.x[j];
-                    td = td || (S.t[j] != 0);
+                    if constexpr (!WT) td = td || (S.t[j] != 0);
                 }
                 double2 o = make_double2(0.0, 0.0);
                 if (cw & (CI_OUT1 | CI_OUT2)) {

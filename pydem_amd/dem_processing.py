@@ -25,7 +25,7 @@ FLAT_ID_INT = -1
 
 _FIELD_OF = {'elev': _ffi.ELEV, 'mag': _ffi.MAG, 'direction': _ffi.DIRECTION, 'flats': _ffi.FLATS,
              'section': _ffi.SECTION, 'proportion': _ffi.PROPORTION, 'uca': _ffi.UCA,
-             'edge_todo': _ffi.EDGE_TODO, 'edge_done': _ffi.EDGE_DONE}
+             'edge_todo': _ffi.EDGE_TODO, 'edge_done': _ffi.EDGE_DONE, 'uca_weighted': _ffi.UCA_WEIGHTED}
 _BOOL_FIELDS = ('flats', 'edge_todo', 'edge_done')
 
 
@@ -118,6 +118,7 @@ class DEMProcessor(object):
     uca = _Resident('uca')
     edge_todo = _Resident('edge_todo')
     edge_done = _Resident('edge_done')
+    uca_weighted = _Resident('uca_weighted')      # last calc_weighted_uca / run_weighted_uca (no counterpart in the reference)
 
     @property
     def twi(self):
@@ -453,6 +454,47 @@ class DEMProcessor(object):
         self.twi_min_area = min(self.twi_min_area, opt.twi_min_area)
         # pits that found a drain are patched into mag/flats by the graph stage (reference :1369-1371)
         self._produced('section', 'proportion', 'uca', 'edge_todo', 'edge_done', 'mag', 'flats')
+
+    def calc_weighted_uca(self, weights, scale_by_cell_area=True):
+        """Weighted flow accumulation along the D-infinity flow graph of calc_uca: the reference's sweep (_calc_uca_chunk
+        :864-987, cyutils.pyx:119-187) started from w * dX2 * dY2 (scale_by_cell_area) or w per cell instead of the cell area,
+        like TauDEM's AreaDinf with a weight grid -- pit drains, the on-edge skip and the circular-drainage re-seed loop
+        included, NaN on flats.  `weights`: a scalar or an array of the tile's shape, any finite values (zero and negative
+        ones too); masked cells count as 0.  With weights = 1 the result is `uca` bit for bit.  Returns the float64 array."""
+        self.run_weighted_uca(weights, scale_by_cell_area)
+        return self.uca_weighted
+
+    def run_weighted_uca(self, weights, scale_by_cell_area=True):
+        """calc_weighted_uca without bringing the result back to the host (the `uca_weighted` attribute).  Leaves uca,
+        mag, flats, the edge masks and twi_min_area alone.  The flow graph is the one calc_uca would build with the current
+        options: the tile's own after calc_uca, built for the call (and not kept) otherwise."""
+        w = self._weights_array(weights)
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if not self._has('direction'):
+            self.run_slopes_directions()
+        self._ensure_tile()
+        self._push('elev', 'mag', 'direction', 'flats')
+        self._tile.upload(_ffi.WEIGHT, w)
+        logger.info("Starting weighted uca calculation")
+        self._tile.uca_weighted(self._options(), scale_by_cell_area)
+        # (a graph the call had to build itself is not kept: section, proportion, mag, flats, edge_todo are as they were)
+        self._produced('uca_weighted')
+
+    def _weights_array(self, weights):
+        """float64 weights of the tile's shape (scalars broadcast, masked cells 0); ValueError before any device work."""
+        shape = tuple(self.shape)
+        if np.ma.isMaskedArray(weights):
+            weights = np.ma.filled(weights.astype(np.float64), 0.0)
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim == 0:
+            w = np.full(shape, float(w))
+        if w.shape != shape:
+            raise ValueError("weights of shape %r for a tile of shape %r" % (w.shape, shape))
+        if not np.isfinite(w).all():
+            raise ValueError("weights must be finite (%d NaN / inf values)" % int((~np.isfinite(w)).sum()))
+        return np.ascontiguousarray(w)
 
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
