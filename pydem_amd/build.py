@@ -1,6 +1,7 @@
 """Build libpydem_hip.so (hipcc, gfx950 only) in-tree: pydem_amd/lib/libpydem_hip.so, and beside it the diagnostic
-libpydem_hip_queue.so (the same objects with uca.hip compiled under -DPYDEM_SWEEP_QUEUE: the frontier-queue sweep schedule that
-tests/test_gpu_sweep_modes.py checks; it refuses some valid inputs, so it is never the product library).
+libpydem_hip_queue.so (the same objects with uca.hip, the per-tile flow accumulation and the only unit that knows the macro, compiled
+under -DPYDEM_SWEEP_QUEUE: the frontier-queue sweep schedule that tests/test_gpu_sweep_modes.py checks; it refuses some valid inputs, so
+it is never the product library).  The cross-tile edge fix-up, uca_edge.hip, is one object in both.
 
     python -m pydem_amd.build [--force]
 
@@ -16,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libpydem_hip.so')
-SOURCES = ['tile.hip', 'stencil.hip', 'flats.hip', 'uca.hip', 'pits.hip', 'synth.hip', 'comm.hip', 'cyutils.hip', 'cond_host.cpp', 'tiff_lzw.cpp', 'cond_device.hip', 'cond_paths.hip']
+SOURCES = ['tile.hip', 'stencil.hip', 'flats.hip', 'uca.hip', 'uca_edge.hip', 'pits.hip', 'synth.hip', 'comm.hip', 'cyutils.hip', 'cond_host.cpp', 'tiff_lzw.cpp', 'cond_device.hip', 'cond_paths.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-fno-fast-math',
          '-Wall', '-Wno-unused-function', '-Wno-unused-result']

@@ -1297,8 +1297,8 @@ int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
         // then on the work lists carry the cells whose neighbourhood changed.  The host looks at the list length every 32
         // sweeps; sweeps over an empty list are no-ops.
         int32_t *cnt = t->counters;
-        PYDEM_TRY(tile_alloc(t, &t->indeg, (size_t)t->NN));
-        int32_t *stamp = t->indeg;
+        PYDEM_TRY(tile_alloc(t, &t->cinfo, (size_t)t->NN));
+        int32_t *stamp = reinterpret_cast<int32_t *>(t->cinfo);      // (the graph-word plane, borrowed for stamps)
         HIP_TRY(hipMemsetAsync(stamp, 0, (size_t)t->NN * 4, t->stream));
         HIP_TRY(hipMemsetAsync(cnt + 2, 0, 6 * sizeof(int32_t), t->stream));
         hipLaunchKernelGGL(k_flat_active, dim3(g1), dim3(256), 0, t->stream, A, R, t->flatlist, nf, 1, al0, cnt + 2);

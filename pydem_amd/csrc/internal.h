@@ -76,9 +76,10 @@ struct pydem_tile {
     bool elev_f32 = false;          // the resident elevation was uploaded as float32: differences are float32 subtractions (stencil, pit drops)
     int elev_dtype = 0;             // pydem_dtype of the last elevation upload (the conditioning keeps the array's dtype where the reference does)
     // graph / sweep scratch
-    uint8_t *inmask = nullptr, *gflags = nullptr, *todo_work = nullptr;   // inmask/gflags: unused since the cinfo word
+    uint8_t *todo_work = nullptr;
     double *contrib = nullptr;     // [2*NN] outgoing contributions per cell (double2)
-    int32_t *indeg = nullptr, *queue[2] = {nullptr, nullptr}, *labels = nullptr, *flatlist = nullptr;
+    uint32_t *cinfo = nullptr;     // [NN] per-cell graph words (uca_graph.h)
+    int32_t *queue[2] = {nullptr, nullptr}, *labels = nullptr, *flatlist = nullptr;
     int32_t *counters = nullptr;       // device scalars
     int32_t *h_counters = nullptr;     // pinned host mirror
     PitGraph pits;
@@ -92,7 +93,7 @@ struct pydem_tile {
     void *nd_rec = nullptr; int64_t nd_cap = 0; int32_t nd = 0;
     int64_t circular_cells = -1;    // cells the last sweep found on / below a drainage loop (-1: no sweep ran on this handle)
     int64_t einc_round = 0;         // incremental edge rounds run on this tile so far (stamps of the NaN flood)
-    bool einc_ready = false;        // incremental edge rounds: counts / deltas / FINAL flags are live (uca.hip K7i)
+    bool einc_ready = false;        // incremental edge rounds: counts / deltas / FINAL flags are live (uca_edge.hip K7i)
     // condensed form of the incremental rounds (uca_cond.inl): the cascade of a round runs on the watched cells only
     std::vector<std::pair<int, int64_t>> watch;     // lines other tiles read (axis, index >= 0); the perimeter is always watched
     size_t watch_built = 0;         // how many of them the live condensed graph covers
@@ -108,7 +109,7 @@ struct pydem_tile {
     int32_t etodo_prev = 0;         // cells whose edge_done byte the previous round cleared (tlist = flatlist)
     double *line_stage = nullptr;   // max(n, m) doubles: staging for column get/set
     void *lines_stage = nullptr; int lines_cap = 0;   // staging for pydem_tile_get_lines
-    bool graph_valid = false;   // inmask/gflags/section/prop/pit lists match the resident elev/dir/flats
+    bool graph_valid = false;   // graph words/section/prop/pit lists match the resident elev/dir/flats
     pydem_options graph_opt = {};   // the options the graph was built with (pydem_uca_weighted reuses it only for the same ones)
     void *scratch = nullptr; size_t scratch_bytes = 0;
     int64_t device_bytes = 0;

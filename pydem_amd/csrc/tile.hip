@@ -1,5 +1,6 @@
 // tile.hip -- handle management, spacing tables, upload/download and the extern "C" surface.
 #include "internal.h"
+#include "uca_graph.h"      // CI_STATIC_MASK, CS_FLAT_SAVE
 #include <cmath>
 #include <math.h>
 #include <stdarg.h>
@@ -170,6 +171,7 @@ template int tile_alloc<double>(pydem_tile *, double **, size_t);
 template int tile_alloc<uint8_t>(pydem_tile *, uint8_t **, size_t);
 template int tile_alloc<int8_t>(pydem_tile *, int8_t **, size_t);
 template int tile_alloc<int32_t>(pydem_tile *, int32_t **, size_t);
+template int tile_alloc<uint32_t>(pydem_tile *, uint32_t **, size_t);
 template int tile_alloc<RowTab>(pydem_tile *, RowTab **, size_t);
 template int tile_alloc<uint16_t>(pydem_tile *, uint16_t **, size_t);
 
@@ -567,8 +569,8 @@ int pydem_tile_destroy(pydem_tile *t)
     // write edge_todo / todo_work / prop: the planes go to the free lists -- i.e. to the next tile -- only once both streams are idle)
     if (t->stream2) (void)hipStreamSynchronize(t->stream2);
     void *ptrs[] = {t->elev, t->mag, t->dir, t->prop, t->uca, t->twi, t->weight, t->uca_w, t->flats, t->edge_todo, t->edge_done,
-                    t->flat0, t->section, t->dX, t->dY, t->dX2, t->dY2, t->rowtab, t->sec_theta, t->row_area, t->inmask,
-                    t->gflags, t->todo_work, t->indeg, t->queue[0], t->queue[1], t->labels, t->flatlist,
+                    t->flat0, t->section, t->dX, t->dY, t->dX2, t->dY2, t->rowtab, t->sec_theta, t->row_area,
+                    t->todo_work, t->cinfo, t->queue[0], t->queue[1], t->labels, t->flatlist,
                     t->counters, t->scratch, t->pits.src, t->pits.dst, t->pits.w, t->pits.in_src,
                     t->pits.in_dst, t->pits.in_w, t->pits.raw_src, t->pits.raw_dst, t->pits.raw_w,
                     t->estamp, t->edelta, t->p_delta, t->s_data, t->p_flags, t->s_flags, t->line_stage, t->contrib,
@@ -984,7 +986,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
         PYDEM_TRY(need(t, PYDEM_FLATS, "pydem_uca_weighted"));
         PYDEM_TRY(need(t, PYDEM_MAG, "pydem_uca_weighted"));
         PYDEM_TRY(ensure_fields(t, {PYDEM_EDGE_TODO, PYDEM_EDGE_DONE}));
-        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(t->counters + 62);      // (scratch of the sweep's counter block)
+        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(t->counters + CS_FLAT_SAVE);
         const int g = (int)(cdiv(t->NN, 256) < 4096 ? cdiv(t->NN, 256) : 4096);
         HIP_TRY(hipMemsetAsync(cnt, 0, 8, t->stream));
         hipLaunchKernelGGL(k_flat_save, dim3(g), dim3(256), 0, t->stream, (const uint8_t *)t->flats, (const double *)t->mag, t->NN,
@@ -1129,15 +1131,14 @@ int pydem_tile_pit_edges(pydem_tile *t, int64_t *n, int32_t *src, int32_t *dst, 
     return 0;
 }
 
-// the static half of the packed graph word of every cell (uca.hip): bits 0-7 in-mask (NW N NE W E SW S SE), 8 / 9 regular
-// out-edge to the facet's first / second neighbour, 10 / 11 pit out- / in-edges, 12-14 facet index
+// the static half of the packed graph word of every cell (layout: uca_graph.h)
 int pydem_tile_graph_words(pydem_tile *t, uint32_t *out)
 {
     HIP_TRY(hipSetDevice(t->device));
-    if (!t->graph_valid || !t->indeg) { pydem_set_error("pydem_tile_graph_words: no flow graph on this tile (pydem_uca / pydem_build_graph first)"); return -3; }
-    HIP_TRY(hipMemcpyAsync(out, t->indeg, (size_t)t->NN * 4, hipMemcpyDeviceToHost, t->stream));
+    if (!t->graph_valid || !t->cinfo) { pydem_set_error("pydem_tile_graph_words: no flow graph on this tile (pydem_uca / pydem_build_graph first)"); return -3; }
+    HIP_TRY(hipMemcpyAsync(out, t->cinfo, (size_t)t->NN * 4, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
-    for (int64_t c = 0; c < t->NN; c++) out[c] &= 0x7FFFu;
+    for (int64_t c = 0; c < t->NN; c++) out[c] &= CI_STATIC_MASK;
     return 0;
 }
 

@@ -99,10 +99,7 @@ __device__ __forceinline__ void cond_seed_cell(const CondArgsE &X, const double 
     const int32_t c = i * m + j;
     bool dn = false, td = false;
     double init = 0.0;
-    if (j == 0) { dn |= sdone[0 * L + i] != 0; init += sdata[0 * L + i] * (double)(sdone[0 * L + i] != 0); td |= stodo[0 * L + i] != 0; }
-    if (j == m - 1) { dn |= sdone[1 * L + i] != 0; init += sdata[1 * L + i] * (double)(sdone[1 * L + i] != 0); td |= stodo[1 * L + i] != 0; }
-    if (i == 0) { dn |= sdone[2 * L + j] != 0; init += sdata[2 * L + j] * (double)(sdone[2 * L + j] != 0); td |= stodo[2 * L + j] != 0; }
-    if (i == n - 1) { dn |= sdone[3 * L + j] != 0; init += sdata[3 * L + j] * (double)(sdone[3 * L + j] != 0); td |= stodo[3 * L + j] != 0; }
+    strip_fold(sdata, sdone, stodo, L, i, j, n, m, dn, td, init);
     const bool own_todo = E.edge_todo[c] != 0;
     const bool own_done = E.edge_done[c] != 0;
     const int32_t w = cond_wid(E, c);

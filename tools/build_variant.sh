@@ -1,6 +1,7 @@
 #!/bin/bash
 # build a variant of the library for a same-box A/B (tools/gpu_ab_lib.sh): tools/build_variant.sh <tag> "<-D flags>" <unit.hip> [<unit.hip> ...]
 # -> pydem_amd/lib/libpydem_hip.so.<tag> = the product objects with the named units recompiled under the extra flags
+# (the sweep's macros are read by uca.hip only, the edge fix-up's -- PYDEM_EINC_PROF, PYDEM_CB_RUN -- by uca_edge.hip only)
 set -e
 TAG=$1; FLAGS=$2; shift 2
 cd "$(dirname "$0")/.."
