@@ -18,6 +18,7 @@
  *   pydem_uca_edge_update     DEMProcessor.calc_uca(uca_init=, edge_init_data=) :724-771,
  *                             _calc_uca_chunk_update :778-862, cyutils.drain_connections
  *                             pydem/cyfuncs/cyutils.pyx:35-72
+ *   pydem_dist_down           downslope distance to a target set / HAND on the same flow graph (reverse sweep) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -173,6 +174,35 @@ int pydem_uca(pydem_tile *t, pydem_options *opt);
  * touched; uca, every other field and all of pydem_uca's timings (the graph stage's included) stay as they were, the next
  * edge round rebuilds its work state.  uca_weighted_ms: seed, level re-arm and weighted sweep, not the graph stage. */
 int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area);
+/* Downslope distance to a target set along the D-infinity flow paths, and with kind = 1, stat = 0 the height above the nearest
+ * drainage (HAND): a reverse (outlet-to-source) sweep over the flow graph pydem_uca sweeps forward (TauDEM's DinfDistDown next
+ * to its AreaDinf; no reference method).  The out-edges of a cell c are the edges of column c of the adjacency matrix of
+ * _mk_adjacency_matrix (pydem/dem_processing.py:1072-1153): the regular edges that survive the keep-filter (:1136-1137), of
+ * weights p and 1 - p, and the pit -> drain edges with theirs.  With T the target set,
+ *     D[c] = 0                      where T[c];
+ *     D[c] = NaN                    otherwise, when c has no out-edge (undrained pits, flats without a drain, cells whose flow
+ *                                   only leaves the tile);
+ *     otherwise, with t_e = D[v_e] + cost(c, v_e) over the out-edges e = c -> v_e of weight w_e,
+ *       stat 0 (ave): D[c] = sum(w_e * t_e) / sum(w_e)   (normalised by the surviving weights: a dropped edge does not bias it)
+ *       stat 1 (min) / 2 (max): the minimum / maximum of t_e, NaN if any t_e is NaN.
+ * NaN propagates upstream in all three: a value is finite only when every flow path from the cell ends in a target inside the
+ * tile (TauDEM's edge-contamination rule).  Cells on or upstream of a drainage cycle (pit edges can close one) never become
+ * ready: they are NaN and counted in *n_unresolved; there is no re-seed loop.
+ * cost(c, v) for c = (r, j), v = (r', j'):  kind 0 (h): hypot((j' - j) * dX2[r], (r' - r) * dY2[r]) -- the source row's cell
+ * size, pit edges of any offset included; kind 1 (v): elev[c] - elev[v], signed, on the tile's float64 elevation, not clamped;
+ * kind 2 (s): hypot(h, v).
+ * Targets: `target`, a host mask [n,m] (non-zero = target), or, when target == NULL, uca >= uca_threshold (finite, >= 0) on the
+ * tile's current uca (pending incremental edge rounds are flushed first, as a download of PYDEM_UCA does; NaN is never a
+ * target).  out: [n,m] host doubles (may be NULL); *ms: device time of the sweep (hipEvent pair); *levels: dependent steps of
+ * the reverse sweep (the initial level, tile passes that finished something, levels of the queue that takes the rest).  One lane finishes a cell from the final values of its out-neighbours in ascending
+ * destination order (a regular edge before a pit edge to the same cell): no floating-point atomics, results identical from
+ * run to run.  Needs the tile's flow graph: -3 when no pydem_uca / pydem_build_graph has run since the elevation, slope,
+ * direction or flats last changed.  Writes no field of the tile, no timing and no state of the forward sweep or of the edge
+ * fix-up: the result plane, a queue and the mask (13 bytes per cell) are the call's own, allocated by the first call and
+ * freed with the tile. */
+int pydem_dist_down(pydem_tile *t, int kind /* 0 h, 1 v, 2 s */, int stat /* 0 ave, 1 min, 2 max */,
+                    const uint8_t *target /* [n,m] host, or NULL */, double uca_threshold /* used when target == NULL */,
+                    double *out /* [n,m] host */, double *ms, int64_t *levels, int64_t *n_unresolved);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

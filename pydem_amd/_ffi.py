@@ -80,6 +80,8 @@ SYMBOLS = {
     'pydem_find_flats': (C.c_int, [_P]),
     'pydem_uca': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_weighted': (C.c_int, [_P, C.POINTER(Options), C.c_int]),
+    'pydem_dist_down': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_edge_update': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
     'pydem_uca_edge_round_inc': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
@@ -277,6 +279,25 @@ class Tile(object):
 
     def uca_weighted(self, opt, scale_by_cell_area=True):
         check(self.lib.pydem_uca_weighted(self._h, C.byref(opt), int(bool(scale_by_cell_area))))
+
+    DIST_KINDS = {'h': 0, 'v': 1, 's': 2}
+    DIST_STATS = {'ave': 0, 'min': 1, 'max': 2}
+
+    def dist_down(self, kind, stat, target=None, uca_threshold=None, download=True):
+        """pydem_dist_down on the tile's flow graph: (float64 [n, m], device ms, levels, unresolved cells).  `target`: a mask
+        of the tile's shape, or None with `uca_threshold`.  download=False: the sweep alone (None instead of the array)."""
+        out = np.empty(self.shape, np.float64) if download else None
+        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        mask = None
+        if target is not None:
+            mask = np.ascontiguousarray(np.asarray(target) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError("target mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        check(self.lib.pydem_dist_down(self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat],
+                                       mask.ctypes.data_as(_P) if mask is not None else None,
+                                       float(uca_threshold) if mask is None else 0.0, out.ctypes.data_as(_P) if download else None,
+                                       C.byref(ms), C.byref(levels), C.byref(left)))
+        return out, ms.value, int(levels.value), int(left.value)
 
     def build_graph(self, opt):
         check(self.lib.pydem_build_graph(self._h, C.byref(opt)))

@@ -111,6 +111,11 @@ struct pydem_tile {
     void *lines_stage = nullptr; int lines_cap = 0;   // staging for pydem_tile_get_lines
     bool graph_valid = false;   // graph words/section/prop/pit lists match the resident elev/dir/flats
     pydem_options graph_opt = {};   // the options the graph was built with (pydem_uca_weighted reuses it only for the same ones)
+    // pydem_dist_down (flowdist.hip): result plane (open cells keep their count of open out-edges in it), queue, target mask,
+    // counter block and its pinned mirror, timing events; allocated by the first call
+    double *dd_out = nullptr; int32_t *dd_queue = nullptr; uint8_t *dd_mask = nullptr;
+    int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
+    hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;
     int64_t device_bytes = 0;
     pydem_timings tm = {};
@@ -144,6 +149,8 @@ void *plane_take(int device, size_t bytes);
 void plane_give(int device, void *q);
 hipError_t dev_malloc(void **p, size_t bytes);      // hipMalloc; on failure the free lists are emptied and the call repeated
 int tile_pinned(pydem_tile *t, size_t bytes, void **out);
+// whole-plane transfer between a device plane and a pageable host array (the tile's stream is drained first)
+int tile_plane_copy(pydem_tile *t, void *dev, void *host, size_t bytes, bool to_host);
 
 // stage entry points implemented in the .hip files
 int stage_stencil(pydem_tile *t);

@@ -574,12 +574,15 @@ int pydem_tile_destroy(pydem_tile *t)
                     t->counters, t->scratch, t->pits.src, t->pits.dst, t->pits.w, t->pits.in_src,
                     t->pits.in_dst, t->pits.in_w, t->pits.raw_src, t->pits.raw_dst, t->pits.raw_w,
                     t->estamp, t->edelta, t->p_delta, t->s_data, t->p_flags, t->s_flags, t->line_stage, t->contrib,
-                    t->eseed, t->lines_stage, t->pits.sort_buf, t->nd_rec, t->cond_mem, t->cb_mem[0], t->cb_mem[1], t->cb_mem[2]};
+                    t->eseed, t->lines_stage, t->pits.sort_buf, t->nd_rec, t->cond_mem, t->cb_mem[0], t->cb_mem[1], t->cb_mem[2],
+                    t->dd_out, t->dd_queue, t->dd_mask, t->dd_ctr};
     for (void *p : ptrs) if (p) plane_give(t->device, p);          // (blocks that did not come from tile_alloc are freed)
     if (t->h_counters) (void)hipHostFree(t->h_counters);
     if (t->h_strip_d) (void)hipHostFree(t->h_strip_d);
     if (t->h_stage) (void)hipHostFree(t->h_stage);
     if (t->h_strip_f) (void)hipHostFree(t->h_strip_f);
+    if (t->dd_h_ctr) (void)hipHostFree(t->dd_h_ctr);
+    for (int i = 0; i < 2; i++) if (t->dd_ev[i]) (void)hipEventDestroy(t->dd_ev[i]);
     for (int i = 0; i < 8; i++) if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);

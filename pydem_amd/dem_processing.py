@@ -496,6 +496,66 @@ class DEMProcessor(object):
             raise ValueError("weights must be finite (%d NaN / inf values)" % int((~np.isfinite(w)).sum()))
         return np.ascontiguousarray(w)
 
+    dist_down = None      # last calc_dist_down (no counterpart in the reference)
+    hand = None           # last calc_hand
+    dist_down_stats = None    # {'ms', 'levels', 'n_unresolved', 'kind', 'stat'} of the last calc_dist_down / calc_hand
+
+    def calc_dist_down(self, target=None, uca_threshold=None, kind='h', stat='ave'):
+        """Distance along the D-infinity flow paths of calc_uca down to the nearest target cells (TauDEM's DinfDistDown; no
+        reference method).  Targets: `target`, a boolean mask of the tile's shape (masked cells are no targets), or
+        `uca_threshold`: the cells with uca >= uca_threshold (the streams) -- exactly one of the two.  kind: 'h' horizontal
+        distance, 'v' drop in elevation (signed), 's' distance along the surface; stat: 'ave' (flow-weighted mean over the
+        out-edges), 'min' or 'max'.  NaN where some flow path from the cell does not end in a target inside the tile (it
+        leaves the tile, or ends in an undrained pit or flat) and on or upstream of a drainage cycle.  Runs on the flow
+        graph of calc_uca (computed first if the tile has none).  Returns the float64 array, kept as `dist_down`."""
+        res = self._dist_down(target, uca_threshold, kind, stat)
+        self.dist_down = res
+        return res
+
+    def calc_hand(self, uca_threshold=None, target=None):
+        """Height above the nearest drainage: calc_dist_down with kind='v', stat='ave'.  Kept as `hand`."""
+        res = self._dist_down(target, uca_threshold, 'v', 'ave')
+        self.hand = res
+        return res
+
+    def _dist_down_target(self, target, uca_threshold, kind, stat):
+        """(mask or None, threshold or None) after the checks that need no device; ValueError otherwise."""
+        if kind not in _ffi.Tile.DIST_KINDS:
+            raise ValueError("kind must be one of 'h', 'v', 's' (got %r)" % (kind,))
+        if stat not in _ffi.Tile.DIST_STATS:
+            raise ValueError("stat must be one of 'ave', 'min', 'max' (got %r)" % (stat,))
+        if (target is None) == (uca_threshold is None):
+            raise ValueError("give exactly one of target (a mask) and uca_threshold")
+        if target is not None:
+            if np.ma.isMaskedArray(target):
+                target = np.ma.filled(target.astype(bool), False)
+            mask = np.asarray(target)
+            if mask.shape != tuple(self.shape):
+                raise ValueError("target of shape %r for a tile of shape %r" % (mask.shape, tuple(self.shape)))
+            return np.ascontiguousarray(mask.astype(bool)), None
+        try:
+            thr = float(uca_threshold)
+        except (TypeError, ValueError):
+            raise ValueError("uca_threshold must be a number (got %r)" % (uca_threshold,))
+        if not np.isfinite(thr) or thr < 0:
+            raise ValueError("uca_threshold must be finite and >= 0 (got %r)" % (uca_threshold,))
+        return None, thr
+
+    def _dist_down(self, target, uca_threshold, kind, stat):
+        mask, thr = self._dist_down_target(target, uca_threshold, kind, stat)
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if self._tile is None or 'uca' not in self._on_device:
+            self.run_uca()                     # the flow graph the distances run on (kept, with uca: nothing is thrown away)
+        self._ensure_tile()
+        logger.info("Starting downslope distance calculation")
+        out, ms, levels, left = self._tile.dist_down(kind, stat, mask, thr)
+        self.dist_down_stats = dict(ms=ms, levels=levels, n_unresolved=left, kind=kind, stat=stat)
+        if left:
+            warnings.warn("%d cells lie on or upstream of a circular drainage pattern: their downslope distance is NaN" % left)
+        return out
+
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
         before stored edge masks are uploaded (the graph stage resets them)."""
