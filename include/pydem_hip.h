@@ -19,6 +19,8 @@
  *                             _calc_uca_chunk_update :778-862, cyutils.drain_connections
  *                             pydem/cyfuncs/cyutils.pyx:35-72
  *   pydem_dist_down           downslope distance to a target set / HAND on the same flow graph (reverse sweep) -- no reference method
+ *   pydem_dist_up             upslope flow-path distance from the divides (longest flow path) on the same flow graph (forward
+ *                             sweep of a path statistic) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -203,6 +205,38 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
 int pydem_dist_down(pydem_tile *t, int kind /* 0 h, 1 v, 2 s */, int stat /* 0 ave, 1 min, 2 max */,
                     const uint8_t *target /* [n,m] host, or NULL */, double uca_threshold /* used when target == NULL */,
                     double *out /* [n,m] host */, double *ms, int64_t *levels, int64_t *n_unresolved);
+/* Upslope flow-path distance: the distance along the D-infinity flow paths from the divides down to each cell -- the forward
+ * (divide-to-outlet) sweep of the path statistic that pydem_dist_down sweeps in reverse (TauDEM's DinfDistUp next to its
+ * DinfDistDown and AreaDinf; no reference method).  stat 2 (max) is the longest flow path into the cell.  The in-edges of a
+ * cell c are the edges u -> c of the adjacency matrix of _mk_adjacency_matrix (pydem/dem_processing.py:1072-1153), the matrix
+ * pydem_dist_down reads: the regular edges that survive the keep-filter (:1136-1137), of weight p or 1 - p of the SOURCE u (c
+ * is u's first or second facet neighbour), and the pit -> drain edges with theirs.  cost(u, c) is pydem_dist_down's cost of
+ * the edge u -> c: for u = (r, j), c = (r', j'): kind 0 (h): hypot((j' - j) * dX2[r], (r' - r) * dY2[r]) -- the SOURCE row's
+ * cell size, pit edges of any offset included; kind 1 (v): elev[u] - elev[c], signed, on the tile's float64 elevation, not
+ * clamped; kind 2 (s): hypot(h, v).
+ *     U[c] = NaN                    where the elevation of c is NaN;
+ *     U[c] = 0                      where c has no in-edge (divides, and isolated cells such as undrained flats without inflow);
+ *     otherwise, once every u_e is final, with t_e = U[u_e] + cost(u_e, c) over the in-edges e = u_e -> c of weight w_e,
+ *       stat 0 (ave): U[c] = sum(w_e * t_e) / sum(w_e)
+ *       stat 1 (min) / 2 (max): the minimum / maximum of t_e;
+ *     NaN if any t_e is NaN.
+ * The in-edges are taken in ascending source order, a regular edge before a pit edge from the same source, by ONE lane per
+ * cell: no floating-point atomics, results identical from run to run and from schedule to schedule.
+ * edge_nan != 0 is TauDEM's edge-contamination rule: a cell on the tile's border (row 0, row n - 1, column 0, column m - 1) is
+ * NaN whatever its in-edges, and so is a cell with an 8-neighbour whose elevation is NaN.  NaN propagates downstream, so a
+ * value is finite only where no flow path into the cell can start outside the tile's data.  With edge_nan == 0 the values are
+ * those of the paths inside the tile: a lower bound for max.
+ * Cells on or downstream of a drainage cycle (pit edges can close one) never become ready: they are NaN and counted in
+ * *n_unresolved; there is no re-seed loop.  (A cell that the edge rule makes NaN is final from the start and not counted.)
+ * out: [n,m] host doubles (may be NULL); *ms: device time of the sweep (hipEvent pair); *levels: dependent steps of the sweep
+ * (the initial level, tile passes that finished something, levels of the queue that takes the rest).  Needs the tile's flow
+ * graph: -3 when no pydem_uca / pydem_build_graph has run since the elevation, slope, direction or flats last changed.
+ * Writes no field of the tile, no timing, no level field of the graph words and no state of the forward sweep or of the edge
+ * fix-up.  Its state is pydem_dist_down's (the result plane and the int32 plane, 12 bytes per cell, and four words per 32 x 32
+ * block; allocated by the first call of either, freed with the tile): a call overwrites the other's result ON THE DEVICE; arrays
+ * already returned are host copies. */
+int pydem_dist_up(pydem_tile *t, int kind /* 0 h, 1 v, 2 s */, int stat /* 0 ave, 1 min, 2 max */, int edge_nan,
+                  double *out /* [n,m] host */, double *ms, int64_t *levels, int64_t *n_unresolved);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

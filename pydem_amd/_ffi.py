@@ -82,6 +82,7 @@ SYMBOLS = {
     'pydem_uca_weighted': (C.c_int, [_P, C.POINTER(Options), C.c_int]),
     'pydem_dist_down': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_int64)]),
+    'pydem_dist_up': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_edge_update': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
     'pydem_uca_edge_round_inc': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
@@ -297,6 +298,15 @@ class Tile(object):
                                        mask.ctypes.data_as(_P) if mask is not None else None,
                                        float(uca_threshold) if mask is None else 0.0, out.ctypes.data_as(_P) if download else None,
                                        C.byref(ms), C.byref(levels), C.byref(left)))
+        return out, ms.value, int(levels.value), int(left.value)
+
+    def dist_up(self, kind, stat, edge_nan=True, download=True):
+        """pydem_dist_up on the tile's flow graph: (float64 [n, m], device ms, levels, unresolved cells).  download=False: the
+        sweep alone (None instead of the array)."""
+        out = np.empty(self.shape, np.float64) if download else None
+        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.pydem_dist_up(self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat], int(bool(edge_nan)),
+                                     out.ctypes.data_as(_P) if download else None, C.byref(ms), C.byref(levels), C.byref(left)))
         return out, ms.value, int(levels.value), int(left.value)
 
     def build_graph(self, opt):

@@ -30,66 +30,11 @@
 // stamps of the passes, then the queue -- every cell enters it at most once, so the segments of all levels fit one after the
 // other), the mask of a call with mask targets (1 B per cell) and four words per tile.  Reads the graph words, proportion,
 // elevation, uca (threshold targets), the pit lists and the spacing; writes nothing else of the tile.
-#include "uca_graph.h"
-#include <math.h>
+// What the forward sweep of the same statistic (flowdist_up.hip, pydem_dist_up) shares with this one -- the state, the encoding,
+// the accumulator, the small kernels and the host's schedule -- is in flowdist.h.
+#include "flowdist.h"
 
 namespace {
-
-constexpr uint32_t DD_OPEN_HI = 0x7FFDD000u;
-constexpr int DD_BATCH = 16;
-constexpr int DD_T = 32, DD_H = DD_T + 2;       // tile edge, tile + halo
-constexpr int DD_MAX_PASSES = 4096;
-constexpr int64_t DD_MIN_PER_VISIT = 16;        // cells a tile visit has to finish on average for another pass to beat the queue
-constexpr int32_t DD_STAMP_OPEN = INT32_MAX;
-constexpr uint16_t DD_FL_OPEN = 0xFFFFu;
-// words of the call's counter block; behind it four words per tile: open cells after its last visit, for each parity of the
-// pass number the last pass of that parity in which it finished something, cells finished by its visit of the current pass
-enum : int { DD_LO = 0, DD_HI = 1, DD_TAIL = 2, DD_LEVELS = 3, DD_NOPEN = 4 /* 64-bit: [4..5] */, DD_PASSDONE = 6 /* 64-bit: [6..7] */,
-             DD_VISITS = 8, DD_WORDS = 16 };
-
-struct DistArgs {
-    const uint32_t *cinfo;
-    const double *prop, *elev, *dX2, *dY2;
-    double *D;
-    int32_t *queue;
-    uint8_t *mask;
-    const int32_t *pit_src, *pit_dst; const double *pit_w;      // out-edges sorted by (src, dst)
-    const int32_t *pin_dst, *pin_src;                          // in-edges sorted by (dst, src)
-    int64_t n_pit;
-    int n, m, kind, stat;
-    int32_t *ctr;
-    int64_t qcap;                                              // queue entries (= cells: every cell enters at most once)
-};
-
-__device__ __forceinline__ double dd_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-__device__ __forceinline__ bool dd_is_open(const DistArgs &A, int32_t c) { return reinterpret_cast<const uint32_t *>(A.D)[2 * (int64_t)c + 1] == DD_OPEN_HI; }
-__device__ __forceinline__ int32_t *dd_count(const DistArgs &A, int32_t c) { return reinterpret_cast<int32_t *>(A.D) + 2 * (int64_t)c; }
-
-// first edge of a sorted pit list whose key is >= `key` (the lists hold a few edges per drained pit: ~17 probes, only for
-// the cells whose graph word carries a pit flag)
-__device__ __forceinline__ int64_t dd_lower_bound(const int32_t *__restrict__ keys, int64_t n, int32_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// wave-aggregated append of the cells that became ready (call from control flow that is uniform per wavefront)
-__device__ __forceinline__ void dd_push(const DistArgs &A, bool pred, int32_t cell)
-{
-    const unsigned long long bal = __ballot(pred);
-    if (bal == 0ull) return;
-    const int lane = (int)__lane_id();
-    const int leader = __ffsll((long long)bal) - 1;
-    int32_t base = 0;
-    if (lane == leader) base = atomicAdd(A.ctr + DD_TAIL, (int32_t)__popcll(bal));
-    base = __shfl(base, leader);
-    const int64_t slot = (int64_t)base + __popcll(bal & ((1ull << lane) - 1ull));
-    if (pred && slot < A.qcap) A.queue[slot] = cell;
-}
 
 // cell v is final: every open cell with an edge into v has one open out-edge less.  `cw` = graph word of v, 0 for a lane
 // that holds no cell.
@@ -112,35 +57,6 @@ __device__ __forceinline__ void dd_release(const DistArgs &A, int32_t v, uint32_
             }
         }
     }
-}
-
-struct DistAcc {
-    double num = 0.0, den = 0.0, lo = INFINITY, hi = -INFINITY;
-    bool nan = false;
-};
-
-// cost of the edge (i, j) -> (i + di, j + dj): dx, dy = cell size of row i, zc / zd = elevation of source / destination
-__device__ __forceinline__ double dd_cost(int kind, int di, int dj, double dx, double dy, double zc, double zd)
-{
-    const double h = kind != 1 ? hypot((double)dj * dx, (double)di * dy) : 0.0;
-    if (kind == 0) return h;
-    const double dz = zc - zd;
-    return kind == 1 ? dz : hypot(h, dz);
-}
-
-__device__ __forceinline__ void dd_add(DistAcc &S, double w, double t)
-{
-    S.num += w * t; S.den += w;
-    S.nan = S.nan || t != t;
-    S.lo = t < S.lo ? t : S.lo;
-    S.hi = t > S.hi ? t : S.hi;
-}
-
-__device__ __forceinline__ double dd_result(int stat, const DistAcc &S)
-{
-    double r = stat == 0 ? S.num / S.den : (stat == 1 ? S.lo : S.hi);
-    if (S.nan || r != r) r = dd_nan();
-    return r;
 }
 
 // one out-edge c = (i, j) -> dst = (i + di, j + dj) of weight w, values from the result plane
@@ -356,25 +272,6 @@ __global__ __launch_bounds__(256) void k_dd_tiles(DistArgs A, int32_t pass, int 
     }
 }
 
-// cells finished and tiles visited by a pass, from the tiles' own words (-1: not visited)
-__global__ __launch_bounds__(256) void k_dd_pass_sum(const int32_t *__restrict__ tile_done, int ntiles, int32_t *ctr)
-{
-    __shared__ int32_t s_cells, s_visits;
-    if (threadIdx.x == 0) { s_cells = 0; s_visits = 0; }
-    __syncthreads();
-    int32_t cells = 0, visits = 0;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < ntiles; k += gridDim.x * blockDim.x) {
-        const int32_t d = tile_done[k];
-        if (d >= 0) { cells += d; visits++; }
-    }
-    if (visits) { atomicAdd(&s_cells, cells); atomicAdd(&s_visits, visits); }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_visits) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(ctr + DD_PASSDONE), (unsigned long long)s_cells);
-        atomicAdd(ctr + DD_VISITS, s_visits);
-    }
-}
-
 // ---- queue
 // every open cell counts its open out-neighbours (all values are from earlier launches); those with none start the queue
 __global__ __launch_bounds__(256) void k_dd_recount(DistArgs A)
@@ -403,16 +300,6 @@ __global__ __launch_bounds__(256) void k_dd_recount(DistArgs A)
     }
 }
 
-// the frontier window moves on: [DD_LO, DD_HI) = what the level before appended
-__global__ void k_dd_advance(int32_t *ctr)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const int32_t lo = ctr[DD_HI], hi = ctr[DD_TAIL];
-        ctr[DD_LO] = lo; ctr[DD_HI] = hi;
-        if (hi > lo) ctr[DD_LEVELS] += 1;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_dd_level(DistArgs A)
 {
     const int64_t lo = A.ctr[DD_LO], hi = A.ctr[DD_HI];
@@ -429,109 +316,27 @@ __global__ __launch_bounds__(256) void k_dd_level(DistArgs A)
     }
 }
 
-// cells that never became ready (on or upstream of a drainage cycle): a plain NaN instead of the count
-__global__ void k_dd_unresolved(double *D, int64_t NN)
-{
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < NN; c += (int64_t)gridDim.x * blockDim.x)
-        if (reinterpret_cast<const uint32_t *>(D)[2 * c + 1] == DD_OPEN_HI) D[c] = dd_nan();
-}
-
 }  // namespace
 
 static int stage_dist_down(pydem_tile *t, int kind, int stat, const uint8_t *target, double threshold, double *out, double *ms,
                            int64_t *levels, int64_t *n_unresolved)
 {
-    const int n = (int)t->n, m = (int)t->m;
-    const int tiles_x = (int)cdiv(m, DD_T), tiles_y = (int)cdiv(n, DD_T);
-    const int64_t ntiles = (int64_t)tiles_x * tiles_y;
-    PYDEM_TRY(tile_alloc(t, &t->dd_out, (size_t)t->NN));
-    PYDEM_TRY(tile_alloc(t, &t->dd_queue, (size_t)t->NN));
-    PYDEM_TRY(tile_alloc(t, &t->dd_ctr, (size_t)(DD_WORDS + 4 * ntiles)));
-    if (!t->dd_h_ctr) HIP_TRY(hipHostMalloc((void **)&t->dd_h_ctr, DD_WORDS * sizeof(int32_t), hipHostMallocDefault));
-    for (int k = 0; k < 2; k++) if (!t->dd_ev[k]) HIP_TRY(hipEventCreate(&t->dd_ev[k]));
     if (target) {
         PYDEM_TRY(tile_alloc(t, &t->dd_mask, (size_t)t->NN));
         PYDEM_TRY(tile_plane_copy(t, t->dd_mask, const_cast<uint8_t *>(target), (size_t)t->NN, false));
     }
 
     DistArgs A;
-    A.cinfo = t->cinfo; A.prop = t->prop; A.elev = t->elev; A.dX2 = t->dX2; A.dY2 = t->dY2;
-    A.D = t->dd_out; A.queue = t->dd_queue; A.mask = t->dd_mask;
-    A.pit_src = t->pits.src; A.pit_dst = t->pits.dst; A.pit_w = t->pits.w;
-    A.pin_dst = t->pits.in_dst; A.pin_src = t->pits.in_src;
-    A.n_pit = t->pits.n_edges;
-    A.n = n; A.m = m; A.kind = kind; A.stat = stat;
-    A.ctr = t->dd_ctr; A.qcap = t->NN;
-    int32_t *tile_state = t->dd_ctr + DD_WORDS;
-
-    // PYDEM_DIST_PASSES=<n>: at most n tile passes (0: the queue alone); PYDEM_DIST_MIN_PER_VISIT=<n>: the switch point (0: tile
-    // passes for as long as one finishes anything).  For tests and timing: the result does not depend on either.
-    static const int max_passes = [] { const char *e = getenv("PYDEM_DIST_PASSES"); const int v = e ? atoi(e) : DD_MAX_PASSES; return v < 0 ? 0 : v; }();
-    static const int64_t min_per_visit = [] { const char *e = getenv("PYDEM_DIST_MIN_PER_VISIT"); return e ? (int64_t)atoll(e) : DD_MIN_PER_VISIT; }();
-    const unsigned gx = (unsigned)cdiv(m, 256), gy = 4096 / gx ? 4096 / gx : 1;
-    const dim3 grid2(gx, gy < (unsigned)n ? gy : (unsigned)n);
-    const int glevel = grid_for(cdiv(t->NN, 4), 2048);
-    volatile int32_t *h = t->dd_h_ctr;
-    auto look = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(t->dd_h_ctr, t->dd_ctr, DD_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        return 0;
-    };
-    auto word64 = [&](int k) { return (int64_t)(((uint64_t)(uint32_t)h[k + 1] << 32) | (uint32_t)h[k]); };
-    HIP_TRY(hipEventRecord(t->dd_ev[0], t->stream));
-    HIP_TRY(hipMemsetAsync(t->dd_ctr, 0, (DD_WORDS + 4 * ntiles) * sizeof(int32_t), t->stream));
-    hipLaunchKernelGGL(k_dd_init, grid2, dim3(256), 0, t->stream, A, target ? (const double *)nullptr : (const double *)t->uca, threshold);
-    HIP_TRY(hipGetLastError());
-    // tile passes while they pay
-    int64_t n_levels = 1, done = 0, visits = 0, n_open = -1;
-    for (int pass = 1; pass <= max_passes; pass++) {
-        hipLaunchKernelGGL(k_dd_tiles, dim3((unsigned)ntiles), dim3(256), 0, t->stream, A, (int32_t)pass, tiles_x, tiles_y, tile_state);
-        hipLaunchKernelGGL(k_dd_pass_sum, dim3(grid_for(ntiles, 256)), dim3(256), 0, t->stream, (const int32_t *)(tile_state + 3 * ntiles), (int)ntiles, t->dd_ctr);
-        HIP_TRY(hipGetLastError());
-        PYDEM_TRY(look());
-        n_open = word64(DD_NOPEN);
-        const int64_t d = word64(DD_PASSDONE) - done, v = (int64_t)h[DD_VISITS] - visits;
-        done += d; visits += v;
-        if (d > 0) n_levels++;
-        if (done >= n_open || d == 0 || d < min_per_visit * v) break;
-    }
-    if (n_open < 0) { PYDEM_TRY(look()); n_open = word64(DD_NOPEN); }
-    // the queue for the rest
-    if (done < n_open) {
-        hipLaunchKernelGGL(k_dd_recount, grid2, dim3(256), 0, t->stream, A);
-        hipLaunchKernelGGL(k_dd_advance, dim3(1), dim3(64), 0, t->stream, t->dd_ctr);
-        HIP_TRY(hipGetLastError());
-        for (;;) {
-            for (int k = 0; k < DD_BATCH; k++) {
-                hipLaunchKernelGGL(k_dd_level, dim3(glevel), dim3(256), 0, t->stream, A);
-                hipLaunchKernelGGL(k_dd_advance, dim3(1), dim3(64), 0, t->stream, t->dd_ctr);
-            }
-            HIP_TRY(hipGetLastError());
-            PYDEM_TRY(look());
-            if (h[DD_HI] == h[DD_LO]) break;         // the last level appended nothing
-        }
-        n_levels += (int64_t)h[DD_LEVELS];
-        done += (int64_t)h[DD_TAIL];
-    }
-    const int64_t left = n_open - done;
-    if (left > 0) {
-        hipLaunchKernelGGL(k_dd_unresolved, dim3(grid_for(t->NN, 2048)), dim3(256), 0, t->stream, t->dd_out, t->NN);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(t->dd_ev[1], t->stream));
-    HIP_TRY(hipEventSynchronize(t->dd_ev[1]));
-    float el = 0.f;
-    HIP_TRY(hipEventElapsedTime(&el, t->dd_ev[0], t->dd_ev[1]));
-    if (ms) *ms = (double)el;
-    if (levels) *levels = n_levels;        // the initial level + tile passes that finished something + levels of the queue
-    if (n_unresolved) *n_unresolved = left;
-    {
-        static const bool dbg = [] { const char *e = getenv("PYDEM_DIST_DEBUG"); return e && atoi(e) > 0; }();
-        if (dbg) fprintf(stderr, "dist_down: %lld open cells, %lld tile visits finished %lld, queue: %d levels, %d cells; %lld unresolved; %.3f ms\n",
-                         (long long)n_open, (long long)visits, (long long)word64(DD_PASSDONE), (int)h[DD_LEVELS], (int)h[DD_TAIL], (long long)left, (double)el);
-    }
-    if (out) PYDEM_TRY(tile_plane_copy(t, t->dd_out, out, (size_t)t->NN * 8, true));
-    return 0;
+    PYDEM_TRY(dist_state(t, A, kind, stat));
+    const dim3 grid2 = dist_row_grid(t);
+    const double *uca = target ? (const double *)nullptr : (const double *)t->uca;
+    return dist_schedule(t, "dist_down", DD_MIN_PER_VISIT, out, ms, levels, n_unresolved,
+        [&] { hipLaunchKernelGGL(k_dd_init, grid2, dim3(256), 0, t->stream, A, uca, threshold); },
+        [&](int pass, int tiles_x, int tiles_y, int32_t *tile_state) {
+            hipLaunchKernelGGL(k_dd_tiles, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, t->stream, A, (int32_t)pass, tiles_x, tiles_y, tile_state);
+        },
+        [&] { hipLaunchKernelGGL(k_dd_recount, grid2, dim3(256), 0, t->stream, A); },
+        [&](int grid) { hipLaunchKernelGGL(k_dd_level, dim3(grid), dim3(256), 0, t->stream, A); });
 }
 
 extern "C" int pydem_dist_down(pydem_tile *t, int kind, int stat, const uint8_t *target, double uca_threshold, double *out, double *ms,

@@ -1,0 +1,328 @@
+// flowdist_up.hip -- K9: upslope flow-path distance on the tile's D-infinity flow graph (TauDEM's DinfDistUp; no counterpart in
+// the reference; semantics: include/pydem_hip.h, pydem_dist_up): the FORWARD (divide-to-outlet) sweep of the path statistic
+// that flowdist.hip sweeps in reverse.  Its `max` is the longest flow path into a cell.
+//
+// A cell is open until every cell with an edge into it is final; then ONE lane finishes it: it PULLS the final values of its
+// in-neighbours in a fixed order (ascending source, a regular edge before a pit edge from the same source), so there are no
+// floating-point atomics and a value does not depend on the schedule that produced it.  The in-neighbours of a cell are bits
+// 0-7 of its graph word (NW N NE W E SW S SE, which is ascending cell order) and its block of the pit in-list; the weight of
+// a regular in-edge from u is p[u] when the cell is u's first (cardinal) facet neighbour and 1 - p[u] when it is the second
+// (diagonal) one; the cost is dd_cost of flowdist.h with u as the source.  State, encoding of an open cell, counters, switches
+// and the host's schedule are those of pydem_dist_down (flowdist.h): a call overwrites the other's device result.
+//
+//   k_du_init: NaN where the elevation is NaN and, under edge_nan, on the tile's border and beside a NaN elevation; 0 where
+//   nothing flows in; the open pattern and the stamp elsewhere.
+//
+//   tile passes (k_du_tiles): one workgroup per 32 x 32 tile, four cells per thread, rounds to the fixed point in LDS with one
+//   barrier each.  A cell has up to eight regular in-edges (the reverse sweep: two out-edges), so their weights and costs do
+//   not fit in registers next to four cells' state; what is staged instead is what they are made of, for tile + halo:
+//   value (8 B), proportion (8 B), elevation (8 B, not loaded for kind h), the round flag (2 B) and the spacing of the 34
+//   rows -- 30.9 KB, which would let five workgroups share a CU's 160 KB; the 158 VGPRs of the inlined evaluation (eight
+//   edges, hypot) allow three (3 wavefronts per SIMD, no scratch).  A cell's weights and costs are computed when it is finished, from LDS alone: once per cell
+//   and call, where operands computed at load time would be computed again at every visit of the tile that leaves the cell
+//   open, and no round waits for global memory.  The exception is a cell with pit in-edges (a drain: about one per pit): it
+//   is opened only when all its pits are final from an earlier pass, and its lane then reads their values and list entries
+//   from global memory in the round that finishes it.  A cell outside the tile is final only if its stamp is from an EARLIER
+//   pass; results and stamps are stored once, after the rounds; one counter update per workgroup.
+//
+//   the queue (k_du_recount, k_du_level): plain Kahn.  k_du_recount writes the number of open in-neighbours into every open
+//   cell's slot and appends the cells with none; a level finishes the cells the previous one appended, then takes one off the
+//   counts of the open cells its one or two regular out-edges and its pit out-edges lead to (integer atomics), and the lane
+//   whose decrement is the last appends that cell.  A value is always written in a launch before the one that reads it.
+#include "flowdist.h"
+
+namespace {
+
+// The switch point of the forward sweep.  What a visit costs is what it stages: 28 B per cell of block + halo here (value,
+// proportion, elevation, stamp) against 12 B in the reverse sweep's (value, stamp), whose switch point of 16 cells per visit
+// was measured; the queue's cost per cell is the same in both directions.  16 * 28 / 12 = 37.
+constexpr int64_t DU_MIN_PER_VISIT = 37;
+
+__device__ __forceinline__ bool du_cardinal(int d) { return NB_DI[d] == 0 || NB_DJ[d] == 0; }
+
+// The value of the open cell c = (i, j) whose in-neighbours are all final.  `reg(d, u, p, du, zu, dx, dy)` hands out what a
+// regular in-edge from neighbour d (cell u) needs: u's proportion, value, elevation and the cell size of u's row -- from the
+// planes (the queue) or from LDS (the tile passes); pit edges always come from the planes.  zc: elevation of c (kind != h).
+template <class Reg>
+__device__ __forceinline__ double du_gather(const DistArgs &A, int32_t c, uint32_t cw, int i, int j, double zc, Reg reg)
+{
+    DistAcc S;
+    int64_t e = A.n_pit;
+    if (cw & CI_PIT_IN) e = dd_lower_bound(A.pin_dst, A.n_pit, c);
+    auto pit = [&](int64_t k) {
+        const int32_t u = A.pin_src[k];
+        const int ui = u / A.m, uj = u - ui * A.m;
+        dd_add(S, A.pin_w[k], A.D[u] + dd_cost(A.kind, i - ui, j - uj, A.dX2[ui], A.dY2[ui], A.kind != 0 ? A.elev[u] : 0.0, zc));
+    };
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        if (!(cw & (1u << d))) continue;
+        const int32_t u = c + NB_DI[d] * A.m + NB_DJ[d];
+        for (; e < A.n_pit && A.pin_dst[e] == c && A.pin_src[e] < u; e++) pit(e);
+        double p, du, zu, dx, dy;
+        reg(d, u, p, du, zu, dx, dy);
+        dd_add(S, du_cardinal(d) ? p : 1 - p, du + dd_cost(A.kind, -NB_DI[d], -NB_DJ[d], dx, dy, zu, zc));
+    }
+    for (; e < A.n_pit && A.pin_dst[e] == c; e++) pit(e);
+    return dd_result(A.stat, S);
+}
+
+__global__ __launch_bounds__(256) void k_du_init(DistArgs A, int edge_nan)
+{
+    unsigned long long *n_open = reinterpret_cast<unsigned long long *>(A.ctr + DD_NOPEN);
+    __shared__ int32_t s_open;
+    if (threadIdx.x == 0) s_open = 0;
+    __syncthreads();
+    int32_t mine = 0;
+    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
+    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
+        const int j = j0 + (int)threadIdx.x;
+        bool open = false;
+        if (j < A.m) {
+            const int32_t c = i * A.m + j;
+            const uint32_t cw = A.cinfo[c];
+            const double z = A.elev[c];
+            bool nanv = z != z;
+            if (edge_nan && !nanv) {
+                nanv = i == 0 || i == A.n - 1 || j == 0 || j == A.m - 1;
+                if (!nanv) {
+#pragma unroll
+                    for (int d = 0; d < 8; d++) { const double zn = A.elev[c + NB_DI[d] * A.m + NB_DJ[d]]; nanv = nanv || zn != zn; }
+                }
+            }
+            open = !nanv && (cw & (0xFFu | CI_PIT_IN));
+            if (open) reinterpret_cast<uint2 *>(A.D)[c] = make_uint2(0u, DD_OPEN_HI);
+            else A.D[c] = nanv ? dd_nan() : 0.0;
+            A.queue[c] = open ? DD_STAMP_OPEN : 0;
+        }
+        mine += open ? 1 : 0;
+    }
+    if (mine) atomicAdd(&s_open, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_open) atomicAdd(n_open, (unsigned long long)s_open);
+}
+
+// ---- tile passes
+__global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state)
+{
+    __shared__ double Dl[DD_H * DD_H], Pl[DD_H * DD_H], El[DD_H * DD_H];
+    __shared__ double Xl[DD_H], Yl[DD_H];
+    __shared__ uint16_t Fl[DD_H * DD_H];        // round of the visit in which the cell became final (0: before it, DD_FL_OPEN: not yet)
+    __shared__ int32_t s_done, s_open;
+    const int ntiles = tiles_x * tiles_y;
+    int32_t *tile_open = tile_state, *prog_w = tile_state + (1 + (pass & 1)) * (int64_t)ntiles, *tile_done = tile_state + 3 * (int64_t)ntiles;
+    const int32_t *prog_r = tile_state + (1 + ((pass - 1) & 1)) * (int64_t)ntiles;
+    const int tile = blockIdx.x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    if (pass > 1) {                                     // (uniform per workgroup: everything read here is from earlier launches)
+        bool visit = false;
+        if (tile_open[tile] > 0)
+            for (int a = -1; a <= 1; a++)
+                for (int b = -1; b <= 1; b++) {
+                    const int yy = ty + a, xx = tx + b;
+                    if (yy >= 0 && yy < tiles_y && xx >= 0 && xx < tiles_x && prog_r[yy * tiles_x + xx] == pass - 1) visit = true;
+                }
+        if (!visit) {
+            if (threadIdx.x == 0) tile_done[tile] = -1;
+            return;
+        }
+    }
+    int32_t *stamp = A.queue;
+    const int i0 = ty * DD_T - 1, j0 = tx * DD_T - 1;
+    if (threadIdx.x == 0) { s_done = 0; s_open = 0; }
+    if (threadIdx.x < DD_H) {
+        const int gi = i0 + (int)threadIdx.x;
+        const bool in = gi >= 0 && gi < A.n;
+        Xl[threadIdx.x] = in ? A.dX2[gi] : 0.0; Yl[threadIdx.x] = in ? A.dY2[gi] : 0.0;
+    }
+    for (int t = threadIdx.x; t < DD_H * DD_H; t += 256) {
+        const int li = t / DD_H, lj = t - li * DD_H;
+        const int gi = i0 + li, gj = j0 + lj;
+        bool fin = false;
+        double d = 0.0, p = 0.0, z = 0.0;
+        if (gi >= 0 && gi < A.n && gj >= 0 && gj < A.m) {
+            const int32_t c = gi * A.m + gj;
+            fin = stamp[c] < pass;                      // (a stamp of this pass, written by whoever owns the cell, reads as open)
+            if (fin) d = A.D[c];
+            p = A.prop[c];
+            if (A.kind != 0) z = A.elev[c];
+        }
+        Dl[t] = d; Pl[t] = p; El[t] = z; Fl[t] = fin ? (uint16_t)0 : DD_FL_OPEN;
+    }
+    __syncthreads();
+    // this thread's cells: k-th cell = row (threadIdx.x / 32) + 8 k of the tile, column threadIdx.x % 32
+    int32_t cell[4];
+    int idx[4];
+    uint32_t word[4], rem[4];
+    double val[4];
+    bool open[4];
+    int n_open = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int ti = (int)(threadIdx.x >> 5) + 8 * k, tj = (int)(threadIdx.x & 31);
+        const int gi = i0 + 1 + ti, gj = j0 + 1 + tj;
+        idx[k] = (ti + 1) * DD_H + tj + 1;
+        open[k] = false; cell[k] = 0; word[k] = 0; rem[k] = 0; val[k] = 0.0;
+        if (gi >= A.n || gj >= A.m || Fl[idx[k]] == 0) continue;
+        const int32_t c = gi * A.m + gj;
+        cell[k] = c;
+        n_open++;
+        const uint32_t cw = A.cinfo[c] & (0xFFu | CI_PIT_IN);
+        if (cw & CI_PIT_IN) {                           // a drain waits until its pits are final from an earlier pass
+            bool settled = true;
+            for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, c); e < A.n_pit && A.pin_dst[e] == c; e++) settled = settled && stamp[A.pin_src[e]] < pass;
+            if (!settled) continue;
+        }
+        word[k] = cw; rem[k] = cw & 0xFFu; open[k] = true;
+    }
+    // Rounds to the fixed point, one barrier each: a cell is ready in round r when all its regular in-neighbours became final
+    // in an EARLIER round (flag < r), so what this round writes -- flags = r, values of cells nobody may read yet -- cannot
+    // change what this round reads.  A lane remembers which in-neighbours it has seen final and asks only for the others.  A
+    // wavefront runs the evaluation as often as its busiest lane has ready cells in the round -- usually once.
+#define DU_SEL(a, k) ((k) == 0 ? a[0] : (k) == 1 ? a[1] : (k) == 2 ? a[2] : a[3])
+    unsigned finished = 0;
+    for (unsigned r = 1;; r++) {                        // (at most 1024 rounds: every round but the last finishes a cell)
+        unsigned fresh = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (!open[k]) continue;
+            uint32_t w = rem[k];
+#pragma unroll
+            for (int d = 0; d < 8; d++)
+                if ((w & (1u << d)) && Fl[idx[k] + NB_DI[d] * DD_H + NB_DJ[d]] < r) w &= ~(1u << d);
+            rem[k] = w;
+            if (w == 0) fresh |= 1u << k;
+        }
+        unsigned todo = fresh;
+        while (todo) {
+            const int k = __ffs((int)todo) - 1;
+            todo &= todo - 1;
+            const int ix = DU_SEL(idx, k);
+            const int32_t c = DU_SEL(cell, k);
+            const int li = ix / DD_H;
+            const double v = du_gather(A, c, DU_SEL(word, k), i0 + li, j0 + ix - li * DD_H, El[ix],
+                [&](int d, int32_t, double &p, double &du, double &zu, double &dx, double &dy) {
+                    const int s = ix + NB_DI[d] * DD_H + NB_DJ[d];
+                    p = Pl[s]; du = Dl[s]; zu = El[s]; dx = Xl[li + NB_DI[d]]; dy = Yl[li + NB_DI[d]];
+                });
+#pragma unroll
+            for (int q = 0; q < 4; q++) val[q] = q == k ? v : val[q];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (fresh & (1u << k)) {
+                Dl[idx[k]] = val[k]; Fl[idx[k]] = (uint16_t)r;
+                open[k] = false;
+                finished |= 1u << k;
+            }
+        if (!__syncthreads_or(fresh != 0)) break;
+    }
+#undef DU_SEL
+    // results leave once, after the rounds
+    int n_done = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (finished & (1u << k)) { A.D[cell[k]] = val[k]; stamp[cell[k]] = pass; n_done++; }
+    if (n_open) atomicAdd(&s_open, n_open - n_done);
+    if (n_done) atomicAdd(&s_done, n_done);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        tile_open[tile] = s_open;
+        if (s_done) prog_w[tile] = pass;
+        tile_done[tile] = s_done;                       // (summed by k_dd_pass_sum)
+    }
+}
+
+// ---- queue
+// every open cell counts its open in-neighbours (all values are from earlier launches); those with none start the queue
+__global__ __launch_bounds__(256) void k_du_recount(DistArgs A)
+{
+    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
+    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
+        const int j = j0 + (int)threadIdx.x;
+        bool ready = false;
+        int32_t c = 0;
+        if (j < A.m) {
+            c = i * A.m + j;
+            if (dd_is_open(A, c)) {
+                const uint32_t cw = A.cinfo[c];
+                int cnt = 0;
+#pragma unroll
+                for (int d = 0; d < 8; d++)
+                    if ((cw & (1u << d)) && dd_is_open(A, c + NB_DI[d] * A.m + NB_DJ[d])) cnt++;
+                if (cw & CI_PIT_IN)
+                    for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, c); e < A.n_pit && A.pin_dst[e] == c; e++)
+                        if (dd_is_open(A, A.pin_src[e])) cnt++;
+                *dd_count(A, c) = cnt;
+                ready = cnt == 0;
+            }
+        }
+        dd_push(A, ready, c);
+    }
+}
+
+// cell v is final: every open cell one of its out-edges leads to has one open in-edge less.  `cw` = graph word of v, 0 for a
+// lane that holds no cell.  (A cell that was final from the start -- NaN by the edge rule -- holds a value, not a count.)
+__device__ __forceinline__ void du_release(const DistArgs &A, int32_t v, uint32_t cw)
+{
+    const int s = ci_section(cw);
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int32_t u = v + (q ? fe2r(s) * A.m + fe2c(s) : fe1r(s) * A.m + fe1c(s));
+        bool ready = false;
+        if ((cw & (q ? CI_OUT2 : CI_OUT1)) && dd_is_open(A, u)) ready = atomicSub(dd_count(A, u), 1) == 1;
+        dd_push(A, ready, u);
+    }
+    if (cw & CI_PIT_OUT) {
+        for (int64_t e = dd_lower_bound(A.pit_src, A.n_pit, v); e < A.n_pit && A.pit_src[e] == v; e++) {
+            const int32_t u = A.pit_dst[e];
+            if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
+                const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
+                if (slot < A.qcap) A.queue[slot] = u;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_du_level(DistArgs A)
+{
+    const int64_t lo = A.ctr[DD_LO], hi = A.ctr[DD_HI];
+    for (int64_t base = lo + (int64_t)blockIdx.x * blockDim.x; base < hi; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = base + threadIdx.x;
+        int32_t v = 0;
+        uint32_t cw = 0;
+        if (k < hi) {
+            v = A.queue[k];
+            cw = A.cinfo[v];
+            const int i = v / A.m;
+            A.D[v] = du_gather(A, v, cw, i, v - i * A.m, A.kind != 0 ? A.elev[v] : 0.0,
+                [&](int d, int32_t u, double &p, double &du, double &zu, double &dx, double &dy) {
+                    p = A.prop[u]; du = A.D[u]; zu = A.kind != 0 ? A.elev[u] : 0.0; dx = A.dX2[i + NB_DI[d]]; dy = A.dY2[i + NB_DI[d]];
+                });
+        }
+        du_release(A, v, cw);
+    }
+}
+
+}  // namespace
+
+extern "C" int pydem_dist_up(pydem_tile *t, int kind, int stat, int edge_nan, double *out, double *ms, int64_t *levels, int64_t *n_unresolved)
+{
+    if (!t) { pydem_set_error("pydem_dist_up: no tile"); return -2; }
+    HIP_TRY(hipSetDevice(t->device));
+    if (kind < 0 || kind > 2 || stat < 0 || stat > 2) { pydem_set_error("pydem_dist_up: kind %d / stat %d out of range (0..2)", kind, stat); return -2; }
+    if (!t->graph_valid || !t->cinfo || !t->prop || !t->have[PYDEM_PROPORTION] || !t->have[PYDEM_ELEV] || !t->spacing_set) {
+        pydem_set_error("pydem_dist_up: no flow graph on this tile (pydem_uca / pydem_build_graph first)");
+        return -3;
+    }
+    DistArgs A;
+    PYDEM_TRY(dist_state(t, A, kind, stat));
+    const dim3 rows = dist_row_grid(t);
+    return dist_schedule(t, "dist_up", DU_MIN_PER_VISIT, out, ms, levels, n_unresolved,
+        [&] { hipLaunchKernelGGL(k_du_init, rows, dim3(256), 0, t->stream, A, edge_nan); },
+        [&](int pass, int tiles_x, int tiles_y, int32_t *tile_state) {
+            hipLaunchKernelGGL(k_du_tiles, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, t->stream, A, (int32_t)pass, tiles_x, tiles_y, tile_state);
+        },
+        [&] { hipLaunchKernelGGL(k_du_recount, rows, dim3(256), 0, t->stream, A); },
+        [&](int grid) { hipLaunchKernelGGL(k_du_level, dim3(grid), dim3(256), 0, t->stream, A); });
+}

@@ -111,8 +111,9 @@ struct pydem_tile {
     void *lines_stage = nullptr; int lines_cap = 0;   // staging for pydem_tile_get_lines
     bool graph_valid = false;   // graph words/section/prop/pit lists match the resident elev/dir/flats
     pydem_options graph_opt = {};   // the options the graph was built with (pydem_uca_weighted reuses it only for the same ones)
-    // pydem_dist_down (flowdist.hip): result plane (open cells keep their count of open out-edges in it), queue, target mask,
-    // counter block and its pinned mirror, timing events; allocated by the first call
+    // pydem_dist_down (flowdist.hip) and pydem_dist_up (flowdist_up.hip), one call at a time: result plane (open cells keep their
+    // count of open out- / in-edges in it), queue, target mask (dist_down with a mask only), counter block and its pinned mirror,
+    // timing events; allocated by the first call of either
     double *dd_out = nullptr; int32_t *dd_queue = nullptr; uint8_t *dd_mask = nullptr;
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};

@@ -556,6 +556,37 @@ class DEMProcessor(object):
             warnings.warn("%d cells lie on or upstream of a circular drainage pattern: their downslope distance is NaN" % left)
         return out
 
+    dist_up = None        # last calc_dist_up (no counterpart in the reference)
+    dist_up_stats = None      # {'ms', 'levels', 'n_unresolved', 'kind', 'stat', 'edge_nan'} of the last calc_dist_up
+
+    def calc_dist_up(self, kind='h', stat='max', edge_nan=True):
+        """Distance along the D-infinity flow paths of calc_uca from the divides down to each cell (TauDEM's DinfDistUp; no
+        reference method); with stat='max' the longest flow path into the cell.  kind: 'h' horizontal distance, 'v' drop in
+        elevation (signed), 's' distance along the surface; stat: 'ave' (flow-weighted mean over the in-edges), 'min' or
+        'max'.  0 where nothing flows into the cell, NaN where the elevation is NaN and on or downstream of a drainage cycle.
+        edge_nan (TauDEM's edge contamination): the tile's border cells and the neighbours of no-data cells are NaN, and so
+        is everything downstream of them -- a value is finite only where no flow path into the cell can start outside the
+        tile's data; edge_nan=False gives the values of the paths inside the tile (a lower bound for 'max').  Runs on the flow
+        graph of calc_uca (computed first if the tile has none).  Returns the float64 array, kept as `dist_up`."""
+        if kind not in _ffi.Tile.DIST_KINDS:
+            raise ValueError("kind must be one of 'h', 'v', 's' (got %r)" % (kind,))
+        if stat not in _ffi.Tile.DIST_STATS:
+            raise ValueError("stat must be one of 'ave', 'min', 'max' (got %r)" % (stat,))
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if self._tile is None or 'uca' not in self._on_device:
+            self.run_uca()                     # the flow graph the distances run on (kept, with uca: nothing is thrown away)
+        self._ensure_tile()
+        logger.info("Starting upslope distance calculation")
+        edge_nan = bool(edge_nan)
+        out, ms, levels, left = self._tile.dist_up(kind, stat, edge_nan)
+        self.dist_up_stats = dict(ms=ms, levels=levels, n_unresolved=left, kind=kind, stat=stat, edge_nan=edge_nan)
+        if left:
+            warnings.warn("%d cells lie on or downstream of a circular drainage pattern: their upslope distance is NaN" % left)
+        self.dist_up = out
+        return out
+
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
         before stored edge masks are uploaded (the graph stage resets them)."""
