@@ -1042,6 +1042,21 @@ static int edge_wide_levels(pydem_tile *t, int32_t cap, int &r, int32_t &last, L
     return 0;
 }
 
+// What PYDEM_EDGE_DEBUG reports of a cascade (host counters around the launches): its levels, how many of them the level
+// kernels ran (a batch that overshoots an emptied frontier included) and how often it passed between the one-workgroup
+// kernel and the level kernels with levels run on both sides.
+struct CascadeDbg {
+    int levels = 0, wide = 0, handovers = 0;
+    int prev = -1;                  // who ran the levels before: 0 the one-workgroup kernel, 1 the level kernels
+    void ran(int kind, int from, int to)
+    {
+        if (to <= from) return;
+        if (prev >= 0 && prev != kind) handovers++;
+        if (kind == 1) wide += to - from;
+        prev = kind; levels = to;
+    }
+};
+
 int stage_edge_update(pydem_tile *t, const pydem_options *opt, const double *const data[4], const uint8_t *const done[4],
                       const uint8_t *const todo[4])
 {
@@ -1122,7 +1137,7 @@ int stage_edge_update(pydem_tile *t, const pydem_options *opt, const double *con
     HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, CS_WINDOW * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     const int32_t nflood = t->h_counters[CS_FRONTIER], nseed = t->h_counters[CS_EDGE_SEEDS];
-    int dbg_rounds[2] = {0, 0}, dbg_wide[2] = {0, 0};
+    CascadeDbg dbg[2];
     auto run_levels = [&](int which, int32_t first) -> int {
         // which: 0 floods, 1 seeded sweep.  The frontier of level 0 is in queue[0] / cnt3[0].
         int r = 0;
@@ -1136,9 +1151,10 @@ int stage_edge_update(pydem_tile *t, const pydem_options *opt, const double *con
                 else hipLaunchKernelGGL(k_edge_small<1>, dim3(1), dim3(1024), 0, t->stream, E, q0, q1, cnt3, r, state);
                 HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, CS_WINDOW * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
                 HIP_TRY(hipStreamSynchronize(t->stream));
+                const int r0 = r;
                 r = t->h_counters[CS_CASCADE_STATE];
                 last = t->h_counters[CS_FRONTIER + r % 3];
-                dbg_rounds[which] = r;
+                dbg[which].ran(0, r0, r);
                 continue;
             }
             const int r0 = r;
@@ -1146,8 +1162,7 @@ int stage_edge_update(pydem_tile *t, const pydem_options *opt, const double *con
                 if (which == 0) hipLaunchKernelGGL(k_edge_level<0>, dim3(grid), dim3(256), 0, t->stream, E, (lv % 2) ? q1 : q0, (lv % 2) ? q0 : q1, cnt3, lv);
                 else hipLaunchKernelGGL(k_edge_level<1>, dim3(grid), dim3(256), 0, t->stream, E, (lv % 2) ? q1 : q0, (lv % 2) ? q0 : q1, cnt3, lv);
             }));
-            dbg_wide[which] += r - r0;
-            dbg_rounds[which] = r;
+            dbg[which].ran(1, r0, r);
         }
         return 0;
     };
@@ -1167,8 +1182,9 @@ int stage_edge_update(pydem_tile *t, const pydem_options *opt, const double *con
     HIP_TRY(hipStreamSynchronize(t->stream));
     t->etodo_prev = t->h_counters[CS_EDGE_CLEARED];
     if (getenv("PYDEM_EDGE_DEBUG"))
-        fprintf(stderr, "edge round: %d seeds, %d todo cells, %d cells reached; levels: floods %d (%d wide), sweep %d (%d wide); %.3f ms\n",
-                nseed, t->h_counters[CS_EDGE_CLEARED], t->h_counters[CS_EDGE_REACHED], dbg_rounds[0], dbg_wide[0], dbg_rounds[1], dbg_wide[1], host_now_ms() - t_begin);
+        fprintf(stderr, "edge round: %d seeds, %d todo cells, %d cells reached; levels: floods %d (%d wide), sweep %d (%d wide); hand-overs %d + %d; %.3f ms\n",
+                nseed, t->h_counters[CS_EDGE_CLEARED], t->h_counters[CS_EDGE_REACHED], dbg[0].levels, dbg[0].wide, dbg[1].levels, dbg[1].wide,
+                dbg[0].handovers, dbg[1].handovers, host_now_ms() - t_begin);
     return 0;
 }
 
@@ -1191,7 +1207,7 @@ static int einc_args(pydem_tile *t, IncArgs &E)
 }
 
 // run the cascade whose first frontier is in queue[0] / counters[CS_FRONTIER]; ONE host synchronisation when the frontier stays small
-static int einc_cascade(pydem_tile *t, const IncArgs &E, int *levels)
+static int einc_cascade(pydem_tile *t, const IncArgs &E, CascadeDbg *dbg)
 {
     int32_t *cnt3 = t->counters + CS_FRONTIER;
     int32_t *state = t->counters + CS_CASCADE_STATE;
@@ -1203,16 +1219,19 @@ static int einc_cascade(pydem_tile *t, const IncArgs &E, int *levels)
         hipLaunchKernelGGL(k_einc_small, dim3(1), dim3(einc_block), 0, t->stream, E, q0, q1, cnt3, r, state);
         HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, CS_WINDOW * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
         HIP_TRY(hipStreamSynchronize(t->stream));
+        const int r_small = r;
         r = t->h_counters[CS_CASCADE_STATE];
+        if (dbg) dbg->ran(0, r_small, r);
         int32_t last = t->h_counters[CS_FRONTIER + r % 3];
         if (last == 0) break;
         // the frontier outgrew one workgroup: level kernels until it is small again
+        const int r_wide = r;
         PYDEM_TRY(edge_wide_levels(t, SMALL_CAP, r, last, [&](int lv, int grid) {
             hipLaunchKernelGGL(k_einc_level, dim3(grid), dim3(256), 0, t->stream, E, (lv % 2) ? q1 : q0, (lv % 2) ? q0 : q1, cnt3, lv);
         }));
+        if (dbg) dbg->ran(1, r_wide, r);
         if (last == 0) break;
     }
-    if (levels) *levels = r;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1230,7 +1249,7 @@ static int cinc_args(pydem_tile *t, CIncArgs &E)
     return 0;
 }
 
-static int cinc_cascade(pydem_tile *t, const CIncArgs &E, int *levels)
+static int cinc_cascade(pydem_tile *t, const CIncArgs &E, CascadeDbg *dbg)
 {
     int32_t *cnt3 = t->counters + CS_FRONTIER;
     int32_t *state = t->counters + CS_CASCADE_STATE;
@@ -1248,19 +1267,22 @@ static int cinc_cascade(pydem_tile *t, const CIncArgs &E, int *levels)
         hipLaunchKernelGGL(k_cinc_apply, dim3(grid_for(E.nd, 1024)), dim3(256), 0, t->stream, E);
         HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, CS_WINDOW * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
         HIP_TRY(hipStreamSynchronize(t->stream));
+        const int r_small = r;
         r = t->h_counters[CS_CASCADE_STATE];
+        if (dbg) dbg->ran(0, r_small, r);
         int32_t last = t->h_counters[CS_FRONTIER + r % 3];
         if (last == 0) break;
         const bool wide = last > cinc_cap;
+        const int r_wide = r;
         PYDEM_TRY(edge_wide_levels(t, cinc_cap, r, last, [&](int lv, int grid) {
             hipLaunchKernelGGL(k_cinc_level, dim3(grid), dim3(256), 0, t->stream, E, (lv % 2) ? q1 : q0, (lv % 2) ? q0 : q1, cnt3, lv);
         }));
+        if (dbg) dbg->ran(1, r_wide, r);
         if (last == 0) {
             if (wide) { hipLaunchKernelGGL(k_cinc_apply, dim3(grid_for(E.nd, 1024)), dim3(256), 0, t->stream, E); HIP_TRY(hipStreamSynchronize(t->stream)); }
             break;
         }
     }
-    if (levels) *levels = r;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1916,12 +1938,15 @@ static int cond_build(pydem_tile *t)
     if (how && !strcmp(how, "check")) return cond_build_check(t);
     int st = -1;
     PYDEM_TRY(cond_build_device(t, &st));
-    if (st < 0) return cond_build_host(t);
+    if (st < 0) {
+        if (getenv("PYDEM_EDGE_DEBUG")) fprintf(stderr, "condensed edge rounds (device build): gave up, the host build takes over\n");
+        return cond_build_host(t);
+    }
     return 0;
 }
 
 // the interior catches up: done watched nodes -> their records, the NaN flood below the nodes it passed, ONE cascade
-static int cond_catchup(pydem_tile *t, int set_done)
+static int cond_catchup(pydem_tile *t, int set_done, CascadeDbg *dbg)
 {
     if (!(t->einc_ready && t->cond_live)) return 0;
     CondArgsE X;
@@ -1932,7 +1957,7 @@ static int cond_catchup(pydem_tile *t, int set_done)
         hipLaunchKernelGGL(k_cond_release, dim3(grid_for(X.nw, 256)), dim3(256), 0, t->stream, X, (QE *)t->queue[0], t->counters + CS_FRONTIER);
         hipLaunchKernelGGL(k_cond_nan_interior, dim3(1), dim3(1024), 0, t->stream, X);
     }
-    PYDEM_TRY(cinc_cascade(t, X.C, nullptr));
+    PYDEM_TRY(cinc_cascade(t, X.C, dbg));
     t->cond_pending = false;
     return 0;
 }
@@ -1941,7 +1966,11 @@ int stage_edge_catchup(pydem_tile *t)
 {
     if (!(t->einc_ready && t->cond_live && t->cond_pending)) return 0;
     HIP_TRY(hipSetDevice(t->device));
-    return cond_catchup(t, 1);
+    CascadeDbg dbg;
+    PYDEM_TRY(cond_catchup(t, 1, &dbg));
+    if (getenv("PYDEM_EDGE_DEBUG"))
+        fprintf(stderr, "condensed edge catch-up (interior cascade): %d levels, %d by the level kernels, %d hand-overs\n", dbg.levels, dbg.wide, dbg.handovers);
+    return 0;
 }
 
 int stage_edge_round_inc(pydem_tile *t, const pydem_options *opt, const double *const data[4], const uint8_t *const done[4],
@@ -1993,7 +2022,7 @@ int stage_edge_round_inc(pydem_tile *t, const pydem_options *opt, const double *
 #ifdef PYDEM_EINC_PROF
     HIP_TRY(hipMemsetAsync(t->counters + CS_EINC_PROF, 0, 8 * sizeof(int32_t), t->stream));
 #endif
-    int levels = 0;
+    CascadeDbg dbg;
     if (t->einc_compact && t->cond_live) {
         // condensed form: seeds + NaN flood + cascade on the watched nodes, two launches and no host look (the edge board's
         // pack kernels follow on the same stream); the interior catches up later (stage_edge_catchup / the flush)
@@ -2022,15 +2051,16 @@ int stage_edge_round_inc(pydem_tile *t, const pydem_options *opt, const double *
         hipLaunchKernelGGL(k_cinc_seed, dim3((unsigned)cdiv(nper, 128)), dim3(128), 0, t->stream, C, t->s_data, t->s_flags,
                            t->s_flags + (size_t)4 * L, L, (QE *)t->queue[0], t->counters + CS_FRONTIER);
         hipLaunchKernelGGL(k_cinc_nan_flood, dim3(1), dim3(1024), 0, t->stream, C);
-        PYDEM_TRY(cinc_cascade(t, C, &levels));
+        PYDEM_TRY(cinc_cascade(t, C, &dbg));
     } else {
         hipLaunchKernelGGL(k_einc_seed, dim3((unsigned)cdiv(nper, 128)), dim3(128), 0, t->stream, E, t->s_data, t->s_flags,
                            t->s_flags + (size_t)4 * L, L, (QE *)t->queue[0], t->counters + CS_FRONTIER);
         hipLaunchKernelGGL(k_einc_nan_flood, dim3(1), dim3(1024), 0, t->stream, E);
-        PYDEM_TRY(einc_cascade(t, E, &levels));
+        PYDEM_TRY(einc_cascade(t, E, &dbg));
     }
     if (getenv("PYDEM_EDGE_DEBUG"))
-        fprintf(stderr, "incremental edge round: %d levels; %.3f ms\n", levels, host_now_ms() - t_begin);
+        fprintf(stderr, "incremental edge round (%s): %d levels, %d by the level kernels, %d hand-overs; %.3f ms\n", t->einc_compact ? "compact" : "cell-indexed",
+                dbg.levels, dbg.wide, dbg.handovers, host_now_ms() - t_begin);
 #ifdef PYDEM_EINC_PROF
     if (getenv("PYDEM_EDGE_DEBUG")) {
         int32_t pr[8];
@@ -2099,37 +2129,43 @@ int stage_edge_flush(pydem_tile *t)
         // condensed form: the interior catches up with what is done, the remaining inlets let go on the watched graph
         // (nothing becomes 'done' any more), and the interior follows once more
         const double t_flush0 = host_now_ms();
-        PYDEM_TRY(cond_catchup(t, 1));
+        CascadeDbg dbg[2];
+        PYDEM_TRY(cond_catchup(t, 1, &dbg[0]));
         CondArgsE X;
         PYDEM_TRY(cond_args(t, X));
         X.C.set_done = 0;
         hipLaunchKernelGGL(k_cond_release_todo, dim3((unsigned)cdiv(nper, 128)), dim3(128), 0, t->stream, X);
         hipLaunchKernelGGL(k_cond_run, dim3(1), dim3(COND_THREADS), 0, t->stream, X);
-        PYDEM_TRY(cond_catchup(t, 0));
+        PYDEM_TRY(cond_catchup(t, 0, &dbg[1]));
         t->einc_ready = false; t->cond_live = false;
         if (getenv("PYDEM_EDGE_DEBUG")) {
             HIP_TRY(hipStreamSynchronize(t->stream));
             int32_t tot[6];
             HIP_TRY(hipMemcpy(tot, t->cond_cnt, sizeof(tot), hipMemcpyDeviceToHost));
-            fprintf(stderr, "condensed edge rounds: flush (interior cascade) %.3f ms; %d rounds ran on the watched graph, %d levels, %d nodes finished\n",
-                    host_now_ms() - t_flush0, tot[4], tot[3], tot[5]);
+            fprintf(stderr, "condensed edge rounds: flush (interior cascade) %.3f ms; %d rounds ran on the watched graph, %d levels, %d nodes finished; "
+                    "interior: %d + %d levels, %d by the level kernels, %d hand-overs\n",
+                    host_now_ms() - t_flush0, tot[4], tot[3], tot[5], dbg[0].levels, dbg[1].levels, dbg[0].wide + dbg[1].wide, dbg[0].handovers + dbg[1].handovers);
         }
         return 0;
     }
     HIP_TRY(hipMemsetAsync(t->counters, 0, CS_WINDOW * sizeof(int32_t), t->stream));
+    CascadeDbg dbg;
     if (t->einc_compact) {
         CIncArgs C;
         PYDEM_TRY(cinc_args(t, C));
         C.set_done = 0;
         hipLaunchKernelGGL(k_cinc_release_todo, dim3((unsigned)cdiv(nper, 128)), dim3(128), 0, t->stream, C, (QE *)t->queue[0], t->counters + CS_FRONTIER);
-        PYDEM_TRY(cinc_cascade(t, C, nullptr));
+        PYDEM_TRY(cinc_cascade(t, C, &dbg));
     } else {
         IncArgs E;
         PYDEM_TRY(einc_args(t, E));
         E.set_done = 0;
         hipLaunchKernelGGL(k_einc_release_todo, dim3((unsigned)cdiv(nper, 128)), dim3(128), 0, t->stream, E, (QE *)t->queue[0], t->counters + CS_FRONTIER);
-        PYDEM_TRY(einc_cascade(t, E, nullptr));
+        PYDEM_TRY(einc_cascade(t, E, &dbg));
     }
+    if (getenv("PYDEM_EDGE_DEBUG"))
+        fprintf(stderr, "incremental edge rounds (%s): flush %d levels, %d by the level kernels, %d hand-overs\n", t->einc_compact ? "compact" : "cell-indexed",
+                dbg.levels, dbg.wide, dbg.handovers);
     t->einc_ready = false;              // counts and deltas are spent: the next incremental round starts from the masks again
     return 0;
 }
