@@ -21,6 +21,8 @@
  *   pydem_dist_down           downslope distance to a target set / HAND on the same flow graph (reverse sweep) -- no reference method
  *   pydem_dist_up             upslope flow-path distance from the divides (longest flow path) on the same flow graph (forward
  *                             sweep of a path statistic) -- no reference method
+ *   pydem_rev_accum           upslope dependence (watersheds) and reverse accumulation on the same flow graph (reverse sweep of a
+ *                             linear or max recursion over the out-edges) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -237,6 +239,39 @@ int pydem_dist_down(pydem_tile *t, int kind /* 0 h, 1 v, 2 s */, int stat /* 0 a
  * already returned are host copies. */
 int pydem_dist_up(pydem_tile *t, int kind /* 0 h, 1 v, 2 s */, int stat /* 0 ave, 1 min, 2 max */, int edge_nan,
                   double *out /* [n,m] host */, double *ms, int64_t *levels, int64_t *n_unresolved);
+/* Reverse accumulation: a linear (op 0) or max (op 1) recursion over the OUT-edges of the D-infinity flow graph, swept from
+ * the outlets to the sources like pydem_dist_down (TauDEM's DinfUpDependence and DinfRevAccum next to its AreaDinf; no
+ * reference method).  The out-edges of a cell c are those pydem_dist_down reads: the regular edges that survive the keep-filter
+ * of _mk_adjacency_matrix (pydem/dem_processing.py:1136-1137), of weights p and 1 - p, and the pit -> drain edges with theirs.
+ * Rules, in this order:
+ *     V[c] = NaN                    where the elevation of c is NaN;
+ *     V[c] = absorb_value           where absorb[c] != 0: the cell is final from the start, its own out-edges do not matter;
+ *     V[c] = seed[c]                where c has no out-edge (undrained pits and flats, cells whose flow only leaves the tile);
+ *     otherwise, once every v_e is final, over the out-edges e = c -> v_e of weight w_e,
+ *       op 0 (sum): acc = 0; acc += w_e * V[v_e]; V[c] = seed[c] + acc   (NOT normalised by the surviving weights: flow that
+ *                   leaves the tile reaches nothing inside it)
+ *       op 1 (max): V[c] = max(seed[c], max_e V[v_e]);
+ *     NaN if any operand is NaN, stored as the canonical NaN.
+ * The out-edges are taken in ascending destination order, a regular edge before a pit edge to the same cell (the order of
+ * pydem_dist_down), by ONE lane per cell that pulls final values: no floating-point atomics, results identical from run to run
+ * and from schedule to schedule.  Cells on or upstream of a drainage cycle (pit edges can close one) never become ready: they
+ * are NaN and counted in *n_unresolved; there is no re-seed loop.
+ * What it is used for: the upslope dependence of a target set T (the share of a cell's flow that reaches T; > 0 is T's
+ * D-infinity watershed) is op 0, seed NULL, absorb = T, absorb_value = 1; the reverse accumulation of a load w (the weighted
+ * sum of w over everything downslope of a cell) is op 0, seed = w, absorb NULL; the maximum downslope load is op 1, seed = w.
+ * seed: [n,m] host doubles, or NULL = 0 everywhere (op 0 only); absorb: [n,m] host mask (non-zero = absorbing), or NULL = none;
+ * absorb_value: finite.  out: [n,m] host doubles (may be NULL); *ms and *levels as for pydem_dist_down: device time of the sweep
+ * (hipEvent pair), and the dependent steps of the reverse sweep (the initial level, tile passes that finished something, levels
+ * of the queue that takes the rest).  -2 for op out of range, op 1 without a seed and a non-finite absorb_value; -3 (no flow
+ * graph) when no pydem_uca / pydem_build_graph has run since the elevation, slope, direction or flats last changed.
+ * Writes no field of the tile, no timing and no state of the forward sweep or of the edge fix-up.  The result plane, the int32
+ * plane, the counter block and the byte mask are pydem_dist_down's (allocated by the first call of any of the three, freed with
+ * the tile): a call overwrites the other calls' result ON THE DEVICE; arrays already returned are host copies.  The seed is one
+ * more plane of the call's own (8 bytes per cell), allocated by the first call that passes a seed and freed with the tile. */
+int pydem_rev_accum(pydem_tile *t, int op /* 0 sum, 1 max */,
+                    const double *seed /* [n,m] host, or NULL = 0 everywhere (op 0 only) */,
+                    const uint8_t *absorb /* [n,m] host mask, or NULL = none */, double absorb_value,
+                    double *out /* [n,m] host, may be NULL */, double *ms, int64_t *levels, int64_t *n_unresolved);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

@@ -83,6 +83,7 @@ SYMBOLS = {
     'pydem_dist_down': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_int64)]),
     'pydem_dist_up': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'pydem_rev_accum': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_edge_update': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
     'pydem_uca_edge_round_inc': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
@@ -307,6 +308,28 @@ class Tile(object):
         ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
         check(self.lib.pydem_dist_up(self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat], int(bool(edge_nan)),
                                      out.ctypes.data_as(_P) if download else None, C.byref(ms), C.byref(levels), C.byref(left)))
+        return out, ms.value, int(levels.value), int(left.value)
+
+    REV_OPS = {'sum': 0, 'max': 1}
+
+    def rev_accum(self, op, seed=None, absorb=None, absorb_value=1.0, download=True):
+        """pydem_rev_accum on the tile's flow graph: (float64 [n, m], device ms, levels, unresolved cells).  op: 'sum' / 0 or
+        'max' / 1; seed: float64 of the tile's shape or None (0 everywhere); absorb: a mask of the tile's shape or None.
+        download=False: the sweep alone (None instead of the array)."""
+        out = np.empty(self.shape, np.float64) if download else None
+        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        sd = mask = None
+        if seed is not None:
+            sd = np.ascontiguousarray(seed, np.float64)
+            if sd.shape != self.shape:
+                raise ValueError("seed of shape %r for a tile of shape %r" % (sd.shape, self.shape))
+        if absorb is not None:
+            mask = np.ascontiguousarray(np.asarray(absorb) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError("absorb mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        check(self.lib.pydem_rev_accum(self._h, int(self.REV_OPS.get(op, op)), sd.ctypes.data_as(_P) if sd is not None else None,
+                                       mask.ctypes.data_as(_P) if mask is not None else None, float(absorb_value),
+                                       out.ctypes.data_as(_P) if download else None, C.byref(ms), C.byref(levels), C.byref(left)))
         return out, ms.value, int(levels.value), int(left.value)
 
     def build_graph(self, opt):

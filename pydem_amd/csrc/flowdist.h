@@ -1,8 +1,10 @@
 // flowdist.h -- what the two sweeps of a path statistic over the tile's flow graph share: the reverse one (flowdist.hip,
 // pydem_dist_down) and the forward one (flowdist_up.hip, pydem_dist_up).  The encoding of an open cell in the result plane,
 // the argument block, the counter words, the wave-aggregated queue append, the accumulator of a cell's edges with its fixed
-// operand order, the edge cost, and the three small kernels both schedules use.  One call at a time owns the state
-// (pydem_tile::dd_*): a call overwrites the other's device result.
+// operand order, the edge cost, and the three small kernels both schedules use.  The reverse accumulation (flowacc_rev.hip,
+// pydem_rev_accum) is a third sweep on the same state and schedule; with the reverse distance it shares the part of the queue
+// that depends on the graph alone (dd_release, k_dd_recount).  One call at a time owns the state (pydem_tile::dd_*): a call
+// overwrites the others' device result.
 #pragma once
 #include "uca_graph.h"
 #include <math.h>
@@ -120,6 +122,57 @@ __global__ void k_dd_advance(int32_t *ctr)
         const int32_t lo = ctr[DD_HI], hi = ctr[DD_TAIL];
         ctr[DD_LO] = lo; ctr[DD_HI] = hi;
         if (hi > lo) ctr[DD_LEVELS] += 1;
+    }
+}
+
+// ---- the queue of a REVERSE sweep (flowdist.hip, flowacc_rev.hip): both depend on the graph alone, not on the statistic
+// cell v is final: every open cell with an edge into v has one open out-edge less.  `cw` = graph word of v, 0 for a lane
+// that holds no cell.
+__device__ __forceinline__ void dd_release(const DistArgs &A, int32_t v, uint32_t cw)
+{
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        const int32_t u = v + NB_DI[d] * A.m + NB_DJ[d];
+        bool ready = false;
+        // (a target upstream of v is final already and holds a value, not a count)
+        if ((cw & (1u << d)) && dd_is_open(A, u)) ready = atomicSub(dd_count(A, u), 1) == 1;
+        dd_push(A, ready, u);
+    }
+    if (cw & CI_PIT_IN) {
+        for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, v); e < A.n_pit && A.pin_dst[e] == v; e++) {
+            const int32_t u = A.pin_src[e];
+            if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
+                const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
+                if (slot < A.qcap) A.queue[slot] = u;
+            }
+        }
+    }
+}
+
+// every open cell counts its open out-neighbours (all values are from earlier launches); those with none start the queue
+__global__ __launch_bounds__(256) void k_dd_recount(DistArgs A)
+{
+    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
+    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
+        const int j = j0 + (int)threadIdx.x;
+        bool ready = false;
+        int32_t c = 0;
+        if (j < A.m) {
+            c = i * A.m + j;
+            if (dd_is_open(A, c)) {
+                const uint32_t cw = A.cinfo[c];
+                const int s = ci_section(cw);
+                int cnt = 0;
+                if ((cw & CI_OUT1) && dd_is_open(A, c + fe1r(s) * A.m + fe1c(s))) cnt++;
+                if ((cw & CI_OUT2) && dd_is_open(A, c + fe2r(s) * A.m + fe2c(s))) cnt++;
+                if (cw & CI_PIT_OUT)
+                    for (int64_t e = dd_lower_bound(A.pit_src, A.n_pit, c); e < A.n_pit && A.pit_src[e] == c; e++)
+                        if (dd_is_open(A, A.pit_dst[e])) cnt++;
+                *dd_count(A, c) = cnt;
+                ready = cnt == 0;
+            }
+        }
+        dd_push(A, ready, c);
     }
 }
 

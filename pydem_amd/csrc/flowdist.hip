@@ -36,29 +36,6 @@
 
 namespace {
 
-// cell v is final: every open cell with an edge into v has one open out-edge less.  `cw` = graph word of v, 0 for a lane
-// that holds no cell.
-__device__ __forceinline__ void dd_release(const DistArgs &A, int32_t v, uint32_t cw)
-{
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        const int32_t u = v + NB_DI[d] * A.m + NB_DJ[d];
-        bool ready = false;
-        // (a target upstream of v is final already and holds a value, not a count)
-        if ((cw & (1u << d)) && dd_is_open(A, u)) ready = atomicSub(dd_count(A, u), 1) == 1;
-        dd_push(A, ready, u);
-    }
-    if (cw & CI_PIT_IN) {
-        for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, v); e < A.n_pit && A.pin_dst[e] == v; e++) {
-            const int32_t u = A.pin_src[e];
-            if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
-                const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
-                if (slot < A.qcap) A.queue[slot] = u;
-            }
-        }
-    }
-}
-
 // one out-edge c = (i, j) -> dst = (i + di, j + dj) of weight w, values from the result plane
 __device__ __forceinline__ void dd_edge(const DistArgs &A, DistAcc &S, int32_t dst, int di, int dj, double w, double dx, double dy, double zc)
 {
@@ -273,33 +250,7 @@ __global__ __launch_bounds__(256) void k_dd_tiles(DistArgs A, int32_t pass, int 
 }
 
 // ---- queue
-// every open cell counts its open out-neighbours (all values are from earlier launches); those with none start the queue
-__global__ __launch_bounds__(256) void k_dd_recount(DistArgs A)
-{
-    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
-    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
-        const int j = j0 + (int)threadIdx.x;
-        bool ready = false;
-        int32_t c = 0;
-        if (j < A.m) {
-            c = i * A.m + j;
-            if (dd_is_open(A, c)) {
-                const uint32_t cw = A.cinfo[c];
-                const int s = ci_section(cw);
-                int cnt = 0;
-                if ((cw & CI_OUT1) && dd_is_open(A, c + fe1r(s) * A.m + fe1c(s))) cnt++;
-                if ((cw & CI_OUT2) && dd_is_open(A, c + fe2r(s) * A.m + fe2c(s))) cnt++;
-                if (cw & CI_PIT_OUT)
-                    for (int64_t e = dd_lower_bound(A.pit_src, A.n_pit, c); e < A.n_pit && A.pit_src[e] == c; e++)
-                        if (dd_is_open(A, A.pit_dst[e])) cnt++;
-                *dd_count(A, c) = cnt;
-                ready = cnt == 0;
-            }
-        }
-        dd_push(A, ready, c);
-    }
-}
-
+// (k_dd_recount and dd_release depend on the graph alone: flowdist.h, shared with flowacc_rev.hip)
 __global__ __launch_bounds__(256) void k_dd_level(DistArgs A)
 {
     const int64_t lo = A.ctr[DD_LO], hi = A.ctr[DD_HI];

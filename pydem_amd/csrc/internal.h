@@ -113,8 +113,10 @@ struct pydem_tile {
     pydem_options graph_opt = {};   // the options the graph was built with (pydem_uca_weighted reuses it only for the same ones)
     // pydem_dist_down (flowdist.hip) and pydem_dist_up (flowdist_up.hip), one call at a time: result plane (open cells keep their
     // count of open out- / in-edges in it), queue, target mask (dist_down with a mask only), counter block and its pinned mirror,
-    // timing events; allocated by the first call of either
+    // timing events; allocated by the first call of either.  pydem_rev_accum (flowacc_rev.hip) runs on the same state (the mask
+    // is its absorbing set) and owns one more plane, its seed, allocated by the first call that passes one
     double *dd_out = nullptr; int32_t *dd_queue = nullptr; uint8_t *dd_mask = nullptr;
+    double *ra_seed = nullptr;
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;

@@ -587,6 +587,95 @@ class DEMProcessor(object):
         self.dist_up = out
         return out
 
+    up_dependence = None          # last calc_up_dependence / calc_watershed (no counterpart in the reference)
+    up_dependence_stats = None    # {'ms', 'levels', 'n_unresolved'} of that call
+    watershed = None              # last calc_watershed
+    rev_accum = None              # last calc_rev_accum: the weighted sum downslope ...
+    rev_accum_max = None          # ... and the maximum downslope
+    rev_accum_stats = None        # {'sum': {'ms', 'levels', 'n_unresolved'}, 'max': {...}} of the two calls behind it
+
+    def _mask_array(self, mask, what):
+        """boolean mask of the tile's shape (masked cells False); ValueError before any device work."""
+        if np.ma.isMaskedArray(mask):
+            mask = np.ma.filled(mask.astype(bool), False)
+        mask = np.asarray(mask)
+        if mask.shape != tuple(self.shape):
+            raise ValueError("%s of shape %r for a tile of shape %r" % (what, mask.shape, tuple(self.shape)))
+        return np.ascontiguousarray(mask.astype(bool))
+
+    def _rev_accum(self, what, op, seed=None, absorb=None):
+        """One pydem_rev_accum call on the flow graph of calc_uca (computed first if the tile has none): (array, stats)."""
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if self._tile is None or 'uca' not in self._on_device:
+            self.run_uca()                     # the flow graph the recursion runs on (kept, with uca: nothing is thrown away)
+        self._ensure_tile()
+        logger.info("Starting %s calculation" % what)
+        out, ms, levels, left = self._tile.rev_accum(op, seed, absorb, 1.0)
+        if left:
+            warnings.warn("%d cells lie on or upstream of a circular drainage pattern: their %s is NaN" % (left, what))
+        return out, dict(ms=ms, levels=levels, n_unresolved=left)
+
+    def calc_up_dependence(self, target):
+        """Upslope dependence on a target set (TauDEM's DinfUpDependence; no reference method): per cell, the fraction of its
+        flow that reaches the targets along the D-infinity flow paths of calc_uca; 1 on the targets, and > 0 exactly on their
+        D-infinity watershed.  `target`: a boolean mask of the tile's shape (masked cells are no targets).  Not normalised:
+        the share of a cell's flow that leaves the tile, or ends in an undrained pit or flat, reaches nothing.  NaN where the
+        elevation is NaN and on or upstream of a drainage cycle.  Runs on the flow graph of calc_uca (computed first if the tile
+        has none).  Returns the float64 array, kept as `up_dependence`; `up_dependence_stats` holds the call's device time, levels
+        and unresolved cells."""
+        mask = self._mask_array(target, 'target')
+        out, st = self._rev_accum('upslope dependence', 'sum', None, mask)
+        self.up_dependence, self.up_dependence_stats = out, st
+        return out
+
+    def calc_watershed(self, outlets, min_fraction=0.0):
+        """The D-infinity watershed of `outlets`: the cells of which more than `min_fraction` (in [0, 1)) of the flow reaches
+        an outlet -- calc_up_dependence and a comparison (NaN is outside, the outlets themselves inside).  `outlets`: a
+        boolean mask of the tile's shape, or a sequence of (row, col) pairs.  Returns the boolean mask, kept as `watershed`;
+        `up_dependence` is set too."""
+        try:
+            frac = float(min_fraction)
+        except (TypeError, ValueError):
+            raise ValueError("min_fraction must be a number in [0, 1) (got %r)" % (min_fraction,))
+        if not (0.0 <= frac < 1.0):
+            raise ValueError("min_fraction must be in [0, 1) (got %r)" % (min_fraction,))
+        shape = tuple(self.shape)
+        arr = outlets if np.ma.isMaskedArray(outlets) else np.asarray(outlets)
+        pairs = arr.ndim == 2 and arr.shape[1] == 2 and arr.dtype.kind in 'iu'
+        if arr.shape == shape and (arr.dtype.kind == 'b' or not pairs):
+            mask = self._mask_array(arr, 'outlets')
+        elif pairs or arr.size == 0:
+            arr = arr.reshape(-1, 2).astype(np.int64)
+            rows, cols = arr[:, 0], arr[:, 1]
+            bad = (rows < 0) | (rows >= shape[0]) | (cols < 0) | (cols >= shape[1])
+            if bad.any():
+                raise ValueError("outlet %r is outside the tile of shape %r" % (tuple(int(v) for v in arr[np.argmax(bad)]), shape))
+            mask = np.zeros(shape, bool)
+            mask[rows, cols] = True
+        else:
+            raise ValueError("outlets must be a mask of shape %r or a sequence of (row, col) pairs of integers (got shape %r, dtype %s)"
+                             % (shape, arr.shape, arr.dtype))
+        dep = self.calc_up_dependence(mask)
+        with np.errstate(invalid='ignore'):
+            self.watershed = dep > frac
+        return self.watershed
+
+    def calc_rev_accum(self, weights):
+        """Reverse accumulation of a per-cell load (TauDEM's DinfRevAccum; no reference method): (racc, dmax), the
+        flow-weighted sum and the maximum of `weights` over the cell itself and everything downslope of it along the
+        D-infinity flow paths of calc_uca.  `weights`: a scalar or an array of the tile's shape, any finite values; masked
+        cells count as 0.  The sum is not normalised: flow that leaves the tile carries nothing back.  NaN where the
+        elevation is NaN and on or upstream of a drainage cycle.  Runs on the flow graph of calc_uca (computed first if the tile
+        has none).  Kept as `rev_accum` and `rev_accum_max`; `rev_accum_stats` holds the stats of both calls."""
+        w = self._weights_array(weights)
+        racc, st_sum = self._rev_accum('reverse accumulation', 'sum', w, None)
+        dmax, st_max = self._rev_accum('maximum downslope load', 'max', w, None)
+        self.rev_accum, self.rev_accum_max = racc, dmax
+        self.rev_accum_stats = dict(sum=st_sum, max=st_max)
+        return racc, dmax
+
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
         before stored edge masks are uploaded (the graph stage resets them)."""
