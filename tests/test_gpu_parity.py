@@ -304,23 +304,12 @@ def test_config1_cone256_device_vs_reference_pinned_oracle():
     _close(dp.mag, o.mag, 'mag'); _close(dp.direction, o.direction, 'direction'); _close(dp.uca, o.uca, 'uca'); _close(twi, twi_o, 'twi')
 
 
-@pytest.mark.parametrize('quantised', [False, True])
-def test_device_edge_set_equals_oracle_adjacency(quantised):
-    """A4 directly: the device never materialises the adjacency matrix of _mk_adjacency_matrix (:1072-1153), it keeps one
-    packed word per cell (in-mask, out flags, facet) plus the pit -> drain side list.  The edge set those words describe
-    -- regular out-edges with weights (proportion, 1 - proportion), pit edges through the same keep-filter (:1136-1137) --
-    must be the oracle's CSC triplets (themselves pinned against scipy's in tests/test_oracle_golden.py): same (source,
-    target) pairs exactly, weights within RTOL, and every edge present in its target's in-mask."""
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor, synth
-    n, m = 310, 270
-    z = synth.fractal(n, m, seed=33, top_shift=6, n_octaves=6, zrange=(35.0 if quantised else 400.0))
-    if quantised:
-        z = np.rint(z)
-    o = O.OracleDEM(z, dX=10.0, dY=12.0, drain_pits=True); o.calc_uca()
+def assert_edge_set_equals_oracle(o, dp):
+    """The edge set the device's graph words and pit list describe (after calc_uca) against the oracle's CSC triplets o.A:
+    the same (source, target) pairs exactly, weights within RTOL, and every regular edge present in its target's in-mask."""
+    n, m = o.elev.shape
+    z = np.asarray(o.elev, np.float64)
     indptr, indices, data = o.A
-    dp = DEMProcessor(elev=z, dX=10.0, dY=12.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-    dp.calc_uca()
     words = dp._tile.graph_words().ravel()
     prop = np.asarray(dp.proportion, float).ravel()
     sec = ((words >> 12) & 7).astype(int)
@@ -356,3 +345,22 @@ def test_device_edge_set_equals_oracle_adjacency(quantised):
         bits = np.array([nb[(-a, -b)] for a, b in zip(ddr.tolist(), ddc.tolist())], np.uint32)
         np.bitwise_or.at(inmask, dst, (1 << bits).astype(np.uint32))
     assert np.array_equal(inmask, words & 0xFF)
+
+
+@pytest.mark.parametrize('quantised', [False, True])
+def test_device_edge_set_equals_oracle_adjacency(quantised):
+    """A4 directly: the device never materialises the adjacency matrix of _mk_adjacency_matrix (:1072-1153), it keeps one
+    packed word per cell (in-mask, out flags, facet) plus the pit -> drain side list.  The edge set those words describe
+    -- regular out-edges with weights (proportion, 1 - proportion), pit edges through the same keep-filter (:1136-1137) --
+    must be the oracle's CSC triplets (themselves pinned against scipy's in tests/test_oracle_golden.py): same (source,
+    target) pairs exactly, weights within RTOL, and every edge present in its target's in-mask."""
+    from oracle import oracle as O
+    from pydem_amd import DEMProcessor, synth
+    n, m = 310, 270
+    z = synth.fractal(n, m, seed=33, top_shift=6, n_octaves=6, zrange=(35.0 if quantised else 400.0))
+    if quantised:
+        z = np.rint(z)
+    o = O.OracleDEM(z, dX=10.0, dY=12.0, drain_pits=True); o.calc_uca()
+    dp = DEMProcessor(elev=z, dX=10.0, dY=12.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
+    dp.calc_uca()
+    assert_edge_set_equals_oracle(o, dp)
