@@ -1098,9 +1098,10 @@ __global__ __launch_bounds__(256) void k_flat_blocks(const int32_t *__restrict__
 }
 
 // books the first arrivals of a pass: a region whose last cell arrived in sweep s0 + j stops there (done = that sweep, like
-// region_arrivals); out[0] = 1 when that happened before the last sweep of the pass (the pass is repeated for its blocks)
+// region_arrivals); out[0] = 1 when that happened before the last sweep of the pass (the pass is repeated for its blocks;
+// whoever raises the flag counts the repeat run in *repeats, a diagnostic)
 __device__ __forceinline__ void flat_accept_rows(const Regions &R, const int32_t *__restrict__ ar_id, int32_t nt, int32_t *arr, int s0, int T, int32_t *out,
-                                                 int first, int stride)
+                                                 int32_t *repeats, int first, int stride)
 {
     for (int32_t k = first; k < nt; k += stride) {
         const int32_t r = ar_id[k];
@@ -1113,7 +1114,7 @@ __device__ __forceinline__ void flat_accept_rows(const Regions &R, const int32_t
                 a[j] = 0;
                 if (!got) continue;
                 left -= got;
-                if (left == 0 && done[r] >= s0) { done[r] = s0 + j; if (j < T - 1) out[0] = 1; }
+                if (left == 0 && done[r] >= s0) { done[r] = s0 + j; if (j < T - 1 && atomicExch(&out[0], 1) == 0) atomicAdd(repeats, 1); }
             }
             rem[r] = left;
         }
@@ -1129,7 +1130,7 @@ __global__ __launch_bounds__(256) void k_flat_accept(Regions R, const int32_t *_
     if (*nblk == 0) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) { *clear_count = 0; *again_next = 0; stats[0] += 1; stats[2] += *nblk; }
     const int32_t nt = *count < cap ? *count : cap;
-    flat_accept_rows(R, ar_id, nt, arr, s0, T, again, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x));
+    flat_accept_rows(R, ar_id, nt, arr, s0, T, again, stats + 1, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x));
 }
 
 // the new surface between the uphill rim and the outlet (:376-380)
@@ -1336,6 +1337,7 @@ int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
         int64_t batch_passes = 0, batch_blocks = 0;
         while (na > 0) {
             bool small_run = false;
+            const char *engine = "wl";
             if (batch_limit > 0 && sweep >= 2 && na <= batch_limit) {
                 if (!b_slot) {
                     const size_t nblocks = (size_t)nbi * nbj;
@@ -1359,10 +1361,13 @@ int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
                 HIP_TRY(hipMemcpyAsync(t->h_counters + 16, cnt + 16, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
                 HIP_TRY(hipStreamSynchronize(t->stream));
                 if (cond_debug > 1) fprintf(stderr, "fill_flats: sweep %d, list %d: %d regions still sweeping, %d blocks\n", sweep, na, t->h_counters[16], t->h_counters[20]);
-                if (t->h_counters[16] > batch_regions) batch_limit = na / 2;      // too many regions still sweeping: more single sweeps first
-                else {
+                if (t->h_counters[16] > batch_regions) {                         // too many regions still sweeping: more single sweeps first
+                    batch_limit = na / 2;
+                    if (cond_debug) fprintf(stderr, "fill_flats: sweep %d: %d regions still sweeping, %d table rows: deferred until the list is at most %d\n",
+                                            sweep, t->h_counters[16], batch_regions, batch_limit);
+                } else {
                     // cnt[20..22]: block counts, rotating (pass k reads [k % 3], appends to [(k + 1) % 3], its k_flat_accept clears [(k + 2) % 3]);
-                    // cnt[28 + k % 2]: the repeat flag of pass k; cnt[24..26]: passes with blocks / (unused) / block visits.
+                    // cnt[28 + k % 2]: the repeat flag of pass k; cnt[24..26]: passes with blocks / passes that ran again / block visits.
                     // The passes are queued CH at a time without a look from the host (a pass without blocks does nothing).
                     int bin = q0;
                     FlatBatch P;
@@ -1392,7 +1397,8 @@ int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
                     batch_passes = t->h_counters[24]; batch_blocks = t->h_counters[26];
                     sweep = sweep_first + (int)batch_passes * batch_T; bin ^= (int)(batch_passes & 1);
                     pp = bin; na = 0;
-                    if (cond_debug) fprintf(stderr, "fill_flats: %lld passes of %d sweeps, %lld block visits\n", (long long)batch_passes, batch_T, (long long)batch_blocks);
+                    if (cond_debug) fprintf(stderr, "fill_flats: %lld passes of %d sweeps from sweep %d, %d ran again, %lld block visits\n", (long long)batch_passes, batch_T,
+                                            sweep_first, t->h_counters[25], (long long)batch_blocks);
                     break;
                 }
             }
@@ -1400,12 +1406,12 @@ int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
                 HIP_TRY(hipMemsetAsync(cnt + 48, 0, sizeof(int32_t), t->stream));      // the barrier's arrival counter: a cache line of its own
                 hipLaunchKernelGGL(k_flat_sweep_coop, dim3((unsigned)(coop_xcd ? coop_wg * 8 : coop_wg)), dim3(256), 0, t->stream, A, R, al[0], al[1], cnt + 4, stamp,
                                    dh[0], dh[1], dl[0], dl[1], sweep, 512, source_tol, cnt + 7, cnt + 48, coop_wg, coop_cap, coop_xcd);
-                small_run = true;
+                small_run = true; engine = "coop";
             } else if (na <= small_cap) {
                 const int ns = 256;
                 hipLaunchKernelGGL(k_flat_sweep_small, dim3(1), dim3(1024), 0, t->stream, A, R, al[0], al[1], cnt + 4, stamp, dh[0], dh[1], dl[0], dl[1],
                                    sweep, ns, source_tol, cnt + 7);
-                small_run = true;
+                small_run = true; engine = "small";
             } else {
                 for (int b = 0; b < 32; b++, sweep++) {
                     const int q = (sweep - 1) & 1;
@@ -1419,7 +1425,7 @@ int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
             pp = cur = (sweep - 1) & 1;
             na = t->h_counters[4 + sweep % 3];
             cell_sweeps += na;
-            if (cond_debug > 1) fprintf(stderr, "fill_flats: sweep %d, list %d\n", sweep, na);
+            if (cond_debug > 1) fprintf(stderr, "fill_flats: sweep %d, list %d (after a %s look)\n", sweep, na, engine);
             if (na > 0 && sweep > sweep_cap + 256) { pydem_set_error("fill_flats: distance sweeps did not terminate"); return -5; }
         }
         if (getenv("PYDEM_COND_DEBUG"))
