@@ -162,6 +162,11 @@ int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_
                     int64_t *n_failed, int64_t *iter_used, int64_t *rounds, int *needs_host);
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
+/* What the tile knows about its flats mask against its slopes, and what the pydem_find_flats calls on it have launched so far
+ * (the call only does the work its result needs; PYDEM_STEP_LEAN=0: always the full pass).  *state: 0 nothing known, 1 flats ==
+ * (mag == -1) everywhere, 2 as 1 except at the pits pydem_tile_restore_pit_slopes has just restored.  counts[3]: calls that ran
+ * the full pass over the tile, calls that only set the restored pits, calls that had nothing to do.  Either pointer may be NULL. */
+int pydem_tile_flats_state(pydem_tile *t, int *state, int64_t *counts);
 int pydem_uca(pydem_tile *t, pydem_options *opt);
 /* Weighted flow accumulation: the sweep of pydem_uca over the same flow graph (pit -> drain edges, the on-edge skip and
  * the circular-drainage re-seed loop included) started from a per-cell seed instead of the cell area --

@@ -78,6 +78,7 @@ SYMBOLS = {
     'pydem_pit_paths': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     'pydem_slopes_directions': (C.c_int, [_P]),
     'pydem_find_flats': (C.c_int, [_P]),
+    'pydem_tile_flats_state': (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     'pydem_uca': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_weighted': (C.c_int, [_P, C.POINTER(Options), C.c_int]),
     'pydem_dist_down': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64),
@@ -239,6 +240,12 @@ class Tile(object):
 
     def find_flats(self):
         check(self.lib.pydem_find_flats(self._h))
+
+    def flats_state(self):
+        """(state, full passes, pit-only passes, elided calls) of pydem_tile_flats_state"""
+        st, cnt = C.c_int(0), (C.c_int64 * 3)()
+        check(self.lib.pydem_tile_flats_state(self._h, C.byref(st), cnt))
+        return st.value, int(cnt[0]), int(cnt[1]), int(cnt[2])
 
     def fill_flats(self, max_pit_area, below_sea, source_tol, peaks, pits, artefacts_only=False):
         """Conditioning on the resident elevation; returns False when the tile must go through the host path (NaN cells)."""

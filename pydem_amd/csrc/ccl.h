@@ -11,8 +11,10 @@
 // one 16 B load; ranks come from a wavefront prefix (shuffles) plus a per-block LDS prefix over
 // the 4 waves, and the block reserves its output range with ONE global atomic per 64 Ki cells
 // (a first version issued one atomic per wavefront on a single address: 22 ms at 16384^2).
+// copy_to (may be null): the mask is also written there as it streams by (flats.hip: the extension starts from a copy of flat0).
 __global__ __launch_bounds__(256) void k_compact_flats(const uint8_t *__restrict__ flat0, int64_t NN,
-                                                       int32_t *__restrict__ list, int32_t *__restrict__ count)
+                                                       int32_t *__restrict__ list, int32_t *__restrict__ count,
+                                                       uint8_t *__restrict__ copy_to)
 {
     // 4 x 64 cells per thread (sixteen 16 B loads), 64 Ki cells per block trip and ONE atomic for them: the counter is a
     // single address, whose returning atomics the L2 serialises at ~12 ns each (16 Ki-cell trips: 16384 atomics = 200 us
@@ -31,6 +33,10 @@ __global__ __launch_bounds__(256) void k_compact_flats(const uint8_t *__restrict
                 uint4 v[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const uint4 *>(flat0 + c0 + 16 * q);
+                if (copy_to) {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) *reinterpret_cast<uint4 *>(copy_to + c0 + 16 * q) = v[q];
+                }
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
@@ -40,7 +46,11 @@ __global__ __launch_bounds__(256) void k_compact_flats(const uint8_t *__restrict
                 }
             } else {
                 for (int k = 0; k < 64; k++)
-                    if (c0 + k < NN && flat0[c0 + k]) bits[j] |= 1ull << k;
+                    if (c0 + k < NN) {
+                        const uint8_t f = flat0[c0 + k];
+                        if (f) bits[j] |= 1ull << k;
+                        if (copy_to) copy_to[c0 + k] = f;
+                    }
             }
             mine[j] = __popcll(bits[j]);
             incl[j] = mine[j];

@@ -1197,7 +1197,7 @@ int label_regions(pydem_tile *t, CondArgs &A, int32_t *nf_out, int32_t *nreg_out
     int32_t *cnt = t->counters;
     HIP_TRY(hipMemsetAsync(cnt, 0, 16 * sizeof(int32_t), t->stream));
     const int big = grid_of(t->NN, 4096);
-    hipLaunchKernelGGL(k_compact_flats, dim3(big), dim3(256), 0, t->stream, A.mask, t->NN, t->flatlist, cnt);
+    hipLaunchKernelGGL(k_compact_flats, dim3(big), dim3(256), 0, t->stream, A.mask, t->NN, t->flatlist, cnt, (uint8_t *)nullptr);
     HIP_TRY(hipMemcpyAsync(t->h_counters, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     const int32_t nf = t->h_counters[0];

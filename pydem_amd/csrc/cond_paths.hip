@@ -748,7 +748,7 @@ int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
     PYDEM_TRY(tile_alloc(t, &t->flatlist, (size_t)t->NN));
     HIP_TRY(hipMemsetAsync(t->counters, 0, 16 * sizeof(int32_t), t->stream));
     hipLaunchKernelGGL(k_paths_pits, dim3(gridp(t->NN, 8192)), dim3(256), 0, t->stream, t->elev, n, m, below_sea, t->flat0, t->counters + 8);
-    hipLaunchKernelGGL(k_compact_flats, dim3(gridp(t->NN, 4096)), dim3(256), 0, t->stream, t->flat0, t->NN, t->flatlist, t->counters);
+    hipLaunchKernelGGL(k_compact_flats, dim3(gridp(t->NN, 4096)), dim3(256), 0, t->stream, t->flat0, t->NN, t->flatlist, t->counters, (uint8_t *)nullptr);
     HIP_TRY(hipMemcpyAsync(t->h_counters, t->counters, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(t->stream));

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 #include <utility>
@@ -110,6 +111,13 @@ struct pydem_tile {
     double *line_stage = nullptr;   // max(n, m) doubles: staging for column get/set
     void *lines_stage = nullptr; int lines_cap = 0;   // staging for pydem_tile_get_lines
     bool graph_valid = false;   // graph words/section/prop/pit lists match the resident elev/dir/flats
+    // What is known about the resident flats mask against the resident slopes (tile.hip: pydem_find_flats only does the work its
+    // result needs).  0: nothing.  1: flats[c] == (mag[c] == -1) for every cell.  2: as 1, except at the cells pits.raw_src[e] >= 0,
+    // e < pits.n_raw, where mag == -1 and flats == 0 (what pydem_tile_restore_pit_slopes leaves behind a state 1).  Every writer of
+    // mag or flats that does not keep one of these sets 0.
+    int flats_state = 0;
+    int64_t find_flats_full = 0, find_flats_patch = 0, find_flats_elided = 0;   // pydem_find_flats calls by what they launched (pydem_tile_flats_state)
+    bool pit_stash_live = false;    // the graph stage left the pit offsets in the (free) area plane: the sweep of pydem_uca does not stash again
     pydem_options graph_opt = {};   // the options the graph was built with (pydem_uca_weighted reuses it only for the same ones)
     // pydem_dist_down (flowdist.hip) and pydem_dist_up (flowdist_up.hip), one call at a time: result plane (open cells keep their
     // count of open out- / in-edges in it), queue, target mask (dist_down with a mask only), counter block and its pinned mirror,
@@ -191,3 +199,11 @@ int stage_synth(pydem_tile *t, uint32_t seed, int64_t row0, int64_t col0, int n_
 int bench_stencil(pydem_tile *t, int iters, double *avg_ms);
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// PYDEM_STEP_LEAN=0 (read per call: the tests switch it): the step as it was before the redundant mask passes, copies and host
+// waits between the big stages were taken out
+static inline bool step_lean()
+{
+    const char *e = getenv("PYDEM_STEP_LEAN");
+    return !(e && *e && atoi(e) == 0);
+}

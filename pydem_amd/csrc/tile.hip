@@ -283,6 +283,13 @@ __global__ void k_convert_to_f64(const S *__restrict__ src, double *__restrict__
     for (; i < n; i += stride) dst[i] = (double)src[i];
 }
 
+// pydem_find_flats behind pydem_tile_restore_pit_slopes: the mask only differs from mag == -1 at the restored pits
+__global__ void k_find_flats_pits(const int32_t *__restrict__ src, int64_t n, uint8_t *flats)
+{
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+        if (src[e] >= 0) flats[src[e]] = 1;
+}
+
 __global__ void k_find_flats(const double *__restrict__ mag, uint8_t *__restrict__ flats, int64_t n)
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -688,6 +695,7 @@ int pydem_tile_upload(pydem_tile *t, int field, const void *src, int dtype)
         HIP_TRY(hipStreamSynchronize(t->stream));
     }
     t->have[field] = true;
+    if (field == PYDEM_MAG || field == PYDEM_FLATS) t->flats_state = 0;
     if (field == PYDEM_ELEV) { t->elev_f32 = (dtype == PYDEM_F32); t->elev_dtype = dtype; }
     if (field == PYDEM_ELEV || field == PYDEM_MAG || field == PYDEM_DIRECTION || field == PYDEM_FLATS) t->graph_valid = false;
     return 0;
@@ -718,6 +726,7 @@ static int line_copy(pydem_tile *t, int field, int axis, int64_t index, void *ho
     const int64_t lim = axis == 0 ? t->n : t->m;
     if (index < 0) index += lim;
     if (index < 0 || index >= lim || (axis != 0 && axis != 1)) { pydem_set_error("line index out of range"); return -2; }
+    if (!to_host && (field == PYDEM_MAG || field == PYDEM_FLATS)) t->flats_state = 0;
     if (to_host && (field == PYDEM_UCA || field == PYDEM_EDGE_DONE || field == PYDEM_EDGE_TODO) && !tile_line_watched(t, axis, index))
         PYDEM_TRY(stage_edge_catchup(t));                       // condensed edge rounds only keep the watched lines current
     char *base = (char *)*pp;
@@ -751,6 +760,7 @@ static int line_copy(pydem_tile *t, int field, int axis, int64_t index, void *ho
     HIP_TRY(hipStreamSynchronize(t->stream));
     if (to_host) memcpy(user, pin, nbytes);
     if (!to_host && (field == PYDEM_ELEV || field == PYDEM_MAG || field == PYDEM_DIRECTION || field == PYDEM_FLATS)) t->graph_valid = false;
+    if (!to_host && (field == PYDEM_MAG || field == PYDEM_FLATS)) t->flats_state = 0;
     return 0;
 }
 
@@ -819,6 +829,7 @@ int pydem_tile_synth_fractal(pydem_tile *t, uint32_t seed, int64_t row0, int64_t
 {
     HIP_TRY(hipSetDevice(t->device));
     t->graph_valid = false;
+    t->flats_state = 0;
     PYDEM_TRY(ensure_field(t, PYDEM_ELEV));
     PYDEM_TRY(stage_synth(t, seed, row0, col0, n_octaves, top_shift, zmin, zrange));
     t->have[PYDEM_ELEV] = true;
@@ -844,8 +855,9 @@ int pydem_slopes_directions(pydem_tile *t)
     PYDEM_TRY(ensure_fields(t, {PYDEM_MAG, PYDEM_DIRECTION, PYDEM_FLATS}));
     PYDEM_TRY(tile_alloc(t, &t->flat0, (size_t)t->NN));
     t->graph_valid = false;
+    t->flats_state = 0;
     PYDEM_TRY(stage_stencil(t));
-    PYDEM_TRY(stage_flats(t));
+    PYDEM_TRY(stage_flats(t));          // (leaves flats_state 1 when flats == (mag == -1) is known to hold)
     t->have[PYDEM_MAG] = t->have[PYDEM_DIRECTION] = t->have[PYDEM_FLATS] = true;
     return 0;
 }
@@ -858,6 +870,7 @@ int pydem_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
     HIP_TRY(hipSetDevice(t->device));
     PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_fill_flats"));
     t->graph_valid = false;
+    t->flats_state = 0;                 // (mag and the other planes are work planes of the conditioning)
     const int r = stage_fill_flats(t, max_pit_area, below_sea, source_tol, peaks, pits, artefacts_only);
     if (r < 0) return r;
     if (needs_host) *needs_host = r;
@@ -869,6 +882,7 @@ int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
 {
     HIP_TRY(hipSetDevice(t->device));
     PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_pit_candidates"));
+    t->flats_state = 0;
     return stage_pit_candidates(t, below_sea, npits);
 }
 
@@ -888,6 +902,7 @@ int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_
     // the path values get the dtype of the array the reference edits (:539): integer surfaces truncate them, float32 ones round
     const int dtype_mode = t->elev_dtype == PYDEM_F64 ? 0 : (t->elev_dtype == PYDEM_F32 ? 2 : 1);
     t->graph_valid = false;
+    t->flats_state = 0;
     const int r = stage_pit_paths(t, order, npits, max_iter, max_dist, max_dist_XY, n_failed, iter_used, rounds, dtype_mode);
     if (r < 0) return r;
     if (needs_host) *needs_host = r;
@@ -900,11 +915,29 @@ int pydem_find_flats(pydem_tile *t)
     t->edge_clean = false;      // these stages reuse the edge-round work lists
     HIP_TRY(hipSetDevice(t->device));
     PYDEM_TRY(need(t, PYDEM_MAG, "pydem_find_flats"));
+    const bool had_flats = t->flats != nullptr;
     PYDEM_TRY(ensure_field(t, PYDEM_FLATS));
-    const int grid = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
-    hipLaunchKernelGGL(k_find_flats, dim3(grid), dim3(256), 0, t->stream, t->mag, t->flats, t->NN);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(t->stream));
+    const bool lean = step_lean();
+    // Only the work the result needs (flats_state, internal.h).  Nothing on the host reads the result, and the stream orders
+    // what follows: no wait.
+    if (lean && had_flats && t->have[PYDEM_FLATS] && t->flats_state == 1) {
+        t->find_flats_elided++;
+    } else if (lean && had_flats && t->have[PYDEM_FLATS] && t->flats_state == 2) {
+        if (t->pits.n_raw > 0) {
+            const int64_t g = cdiv(t->pits.n_raw, 256);
+            hipLaunchKernelGGL(k_find_flats_pits, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, t->stream,
+                               (const int32_t *)t->pits.raw_src, t->pits.n_raw, t->flats);
+            HIP_TRY(hipGetLastError());
+        }
+        t->find_flats_patch++;
+    } else {
+        const int grid = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
+        hipLaunchKernelGGL(k_find_flats, dim3(grid), dim3(256), 0, t->stream, t->mag, t->flats, t->NN);
+        HIP_TRY(hipGetLastError());
+        if (!lean) HIP_TRY(hipStreamSynchronize(t->stream));
+        t->find_flats_full++;
+    }
+    t->flats_state = 1;
     t->have[PYDEM_FLATS] = true;
     return 0;
 }
@@ -920,9 +953,18 @@ int pydem_uca(pydem_tile *t, pydem_options *opt)
     PYDEM_TRY(need(t, PYDEM_FLATS, "pydem_uca"));
     if (!t->spacing_set) { pydem_set_error("pydem_uca: call pydem_tile_set_spacing first"); return -3; }
     PYDEM_TRY(ensure_fields(t, {PYDEM_SECTION, PYDEM_PROPORTION, PYDEM_UCA, PYDEM_EDGE_TODO, PYDEM_EDGE_DONE}));
-    PYDEM_TRY(stage_section_graph(t, opt));
+    // the area plane is free from here to the sweep: the graph stage may leave the pit offsets in it (uca.hip: k_graph_add_pits)
+    t->pit_stash_live = step_lean();
+    {
+        const int rc = stage_section_graph(t, opt);
+        if (rc != 0) { t->pit_stash_live = false; return rc; }
+    }
     t->graph_valid = true;
-    PYDEM_TRY(stage_sweep(t, opt));
+    {
+        const int rc = stage_sweep(t, opt);
+        t->pit_stash_live = false;
+        if (rc != 0) return rc;
+    }
     // record minimum area (dem_processing.py:897-899)
     double mn = opt->twi_min_area;
     for (int64_t i = 0; i < t->n; i++) {
@@ -945,6 +987,7 @@ static int ensure_graph(pydem_tile *t, pydem_options *opt, const char *who)
     PYDEM_TRY(need(t, PYDEM_DIRECTION, who));
     if (!t->spacing_set) { pydem_set_error("%s: call pydem_tile_set_spacing first", who); return -3; }
     PYDEM_TRY(ensure_fields(t, {PYDEM_SECTION, PYDEM_PROPORTION}));
+    t->pit_stash_live = false;          // (the area plane holds the tile's uca on this path: the sweeps stash on their own)
     PYDEM_TRY(stage_section_graph(t, opt));
     t->graph_valid = true;
     t->have[PYDEM_SECTION] = t->have[PYDEM_PROPORTION] = true;
@@ -1042,6 +1085,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
         HIP_TRY(hipStreamSynchronize(t->stream));
         t->graph_valid = false;
     }
+    if (own_graph) t->flats_state = 0;      // (the graph stage patched mag / flats and they were written back: nothing is claimed about them)
     if (rc != 0) return rc;
     t->have[PYDEM_UCA_WEIGHTED] = true;
     return 0;
@@ -1150,11 +1194,22 @@ int pydem_tile_restore_pit_slopes(pydem_tile *t)
     t->edge_clean = false;      // these stages reuse the edge-round work lists
     HIP_TRY(hipSetDevice(t->device));
     if (t->pits.n_raw == 0) return 0;
+    // mag becomes -1 at the listed pits and flats is left alone (callers read it between this call and the next pydem_find_flats):
+    // behind a state 1 the mask then differs from mag == -1 at those cells only, and only where it holds 0 -- state 2, whatever the
+    // list is; from any other state nothing is known
+    t->flats_state = (t->flats_state == 1) ? 2 : 0;
     const int64_t g = cdiv(t->pits.n_raw, 256);
     hipLaunchKernelGGL(k_restore_pit_slopes, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, t->stream, t->pits.raw_src,
                        t->pits.n_raw, t->mag);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(t->stream));
+    if (!step_lean()) HIP_TRY(hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+int pydem_tile_flats_state(pydem_tile *t, int *state, int64_t *counts)
+{
+    if (state) *state = t->flats_state;
+    if (counts) { counts[0] = t->find_flats_full; counts[1] = t->find_flats_patch; counts[2] = t->find_flats_elided; }
     return 0;
 }
 
@@ -1167,6 +1222,7 @@ int pydem_bench_stencil(pydem_tile *t, int iters, double *avg_ms)
     if (!t->spacing_set) { pydem_set_error("pydem_bench_stencil: call pydem_tile_set_spacing first"); return -3; }
     PYDEM_TRY(ensure_fields(t, {PYDEM_MAG, PYDEM_DIRECTION}));
     PYDEM_TRY(tile_alloc(t, &t->flat0, (size_t)t->NN));
+    t->flats_state = 0;                 // (the stencil rewrites mag without the flats stage behind it)
     return bench_stencil(t, iters, avg_ms);
 }
 

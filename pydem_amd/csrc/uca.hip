@@ -141,12 +141,21 @@ __global__ __launch_bounds__(256) void k_graph_inmask(const double *__restrict__
 }
 
 // pit edges contribute to in-degrees, flags and the corner sums
+// STASH (pydem_uca only, where the area plane is free until the sweep): the walk also leaves {first in-edge, first out-edge} of
+// every pit source / drain in the cell's area slot, what k_pit_stash (below) does in a walk of its own over the same lists
+template <bool STASH>
 __global__ void k_graph_add_pits(const int32_t *__restrict__ src, const int32_t *__restrict__ dst,
                                  const double *__restrict__ w, int64_t ne, int n, int m,
-                                 uint32_t *cinfo, double *corner_sums)
+                                 uint32_t *cinfo, double *corner_sums, const int32_t *__restrict__ pin_dst, double *area)
 {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += (int64_t)gridDim.x * blockDim.x) {
         const int32_t s = src[e], d = dst[e];
+        if (STASH) {
+            int32_t *slots = reinterpret_cast<int32_t *>(area);
+            const int32_t pd = pin_dst[e];
+            if (e == 0 || pin_dst[e - 1] != pd) slots[2 * (int64_t)pd] = (int32_t)e;
+            if (e == 0 || src[e - 1] != s) slots[2 * (int64_t)s + 1] = (int32_t)e;
+        }
         atomicOr(&cinfo[s], CI_PIT_OUT);
         atomicOr(&cinfo[d], CI_PIT_IN | (CI_LEVEL_INF << CI_LEVEL_SHIFT));   // a pit drains here: not a source
         const int corners[4] = {0, m - 1, (n - 1) * m, (n - 1) * m + m - 1};
@@ -1916,6 +1925,8 @@ int stage_section_graph(pydem_tile *t, const pydem_options *opt)
     const dim3 grid2((unsigned)(cdiv(m, 256) < 64 ? cdiv(m, 256) : 64), (unsigned)(n < 16384 ? n : 16384));
     t->tm.n_pit_edges = 0; t->tm.n_pits_undrained = 0; t->tm.pits_ms = 0;
     t->pits.n_edges = 0; t->pits.n_raw = 0;
+    if (t->flats_state == 2) t->flats_state = 0;      // (state 2 is stated on the pit list that goes here; the pit search itself keeps
+                                                      // state 1: it writes a mean of non-negative slopes and flats = 0 at the same cells)
     // The section / out-flag kernel and the in-mask kernel are streaming kernels that share nothing with the pit search
     // (bound by instruction issue, little memory traffic) except the flats mask: the reference derives section and
     // proportion from the mask as it is BEFORE the pits are patched (:1021-1070 runs ahead of _mk_adjacency_matrix).  A
@@ -1942,9 +1953,17 @@ int stage_section_graph(pydem_tile *t, const pydem_options *opt)
     if (opt->drain_pits) PYDEM_TRY(stage_pits(t, opt));
     HIP_TRY(hipEventRecord(t->ev[2], t->stream));
     HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0));
+    const bool stash = t->pit_stash_live && t->uca != nullptr;     // (pydem_uca asked for it: tile.hip)
+    t->pit_stash_live = false;
     if (t->pits.n_edges > 0) {
-        hipLaunchKernelGGL(k_graph_add_pits, dim3(grid_for(t->pits.n_edges, 1024)), dim3(256), 0, t->stream, t->pits.src,
-                           t->pits.dst, t->pits.w, t->pits.n_edges, n, m, t->cinfo, corner_sums);
+        if (stash) {
+            hipLaunchKernelGGL(k_graph_add_pits<true>, dim3(grid_for(t->pits.n_edges, 1024)), dim3(256), 0, t->stream, t->pits.src,
+                               t->pits.dst, t->pits.w, t->pits.n_edges, n, m, t->cinfo, corner_sums, (const int32_t *)t->pits.in_dst, t->uca);
+            t->pit_stash_live = true;
+        } else {
+            hipLaunchKernelGGL(k_graph_add_pits<false>, dim3(grid_for(t->pits.n_edges, 1024)), dim3(256), 0, t->stream, t->pits.src,
+                               t->pits.dst, t->pits.w, t->pits.n_edges, n, m, t->cinfo, corner_sums, (const int32_t *)nullptr, (double *)nullptr);
+        }
     }
     hipLaunchKernelGGL(k_corner_todo, dim3(1), dim3(64), 0, t->stream, corner_sums, t->elev, n, m, t->edge_todo, t->todo_work);
     HIP_TRY(hipEventRecord(t->ev[3], t->stream));
@@ -2059,7 +2078,9 @@ static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
     SweepArgs A;
     fill_sweep_args(t, A);
     if (WT) { A.a0 = seed; A.area = t->uca_w; }
-    if (A.n_pit > 0)   // the unused area slots of pit sources / drains carry their edge-list offsets until they are processed
+    const bool stashed = !WT && t->pit_stash_live;      // (the graph stage of this pydem_uca has done it in its walk over the pit edges)
+    if (!WT) t->pit_stash_live = false;
+    if (A.n_pit > 0 && !stashed)   // the unused area slots of pit sources / drains carry their edge-list offsets until they are processed
         hipLaunchKernelGGL(k_pit_stash, dim3(grid_for(A.n_pit, 2048)), dim3(256), 0, t->stream, A.pin_dst, A.pit_src, A.n_pit, A.area);
     // ---- tile-local passes until they stop paying, then the queue rounds take over
     const int tiles_x = (int)cdiv(m, TT), tiles_total = tiles_x * (int)cdiv(n, TH);
