@@ -1,10 +1,19 @@
-// flowdist.h -- what the two sweeps of a path statistic over the tile's flow graph share: the reverse one (flowdist.hip,
-// pydem_dist_down) and the forward one (flowdist_up.hip, pydem_dist_up).  The encoding of an open cell in the result plane,
-// the argument block, the counter words, the wave-aggregated queue append, the accumulator of a cell's edges with its fixed
-// operand order, the edge cost, and the three small kernels both schedules use.  The reverse accumulation (flowacc_rev.hip,
-// pydem_rev_accum) is a third sweep on the same state and schedule; with the reverse distance it shares the part of the queue
-// that depends on the graph alone (dd_release, k_dd_recount).  One call at a time owns the state (pydem_tile::dd_*): a call
-// overwrites the others' device result.
+// flowdist.h -- the engine of the three sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
+// pydem_dist_down), the forward one (flowdist_up.hip, pydem_dist_up) and the reverse accumulation (flowacc_rev.hip,
+// pydem_rev_accum).  A sweep supplies what differs -- which cells are final at the start (a Classify), the value of a cell whose
+// neighbours are final (a Finish; in the tile passes, its round loop) and which side of the graph it waits for -- and takes
+// the rest from here, where every rule is written once:
+//
+//   the encoding of an open cell in the result plane, the argument block, the counter words, the wave-aggregated queue append;
+//   the accumulator of a path statistic with its fixed operand order, the edge cost;
+//   a cell's block of a sorted pit list (dd_pit_block), its facet neighbours in cell order (dd_facet_sorted) and its out-edges
+//   in the order every reverse sweep pulls them in (dd_for_out_edges);
+//   the frame of a tile visit: whether it runs, the staging of tile + halo under the stamp rule, the geometry of a thread's
+//   four cells, the store after the rounds and the tile's three words (dd_visit_begin, dd_stage, dd_slot, dd_visit_end);
+//   the init and the level kernel (k_flow_init, k_flow_level), the queue of a reverse sweep (dd_release, k_dd_recount);
+//   the host's checks, uploads, state and schedule (dist_check_tile, dist_check_graph, dist_upload, dist_state, dist_schedule, dist_sweep).
+//
+// One call at a time owns the state (pydem_tile::dd_*): a call overwrites the others' device result.
 #pragma once
 #include "uca_graph.h"
 #include <math.h>
@@ -53,6 +62,19 @@ __device__ __forceinline__ int64_t dd_lower_bound(const int32_t *__restrict__ ke
     return lo;
 }
 
+// The block of a sorted pit list whose key is `c`, walked with `for (PitBlock b = dd_pit_block(keys, n, c); b.more(); b.e++)`;
+// has = false (the cell's graph word carries no pit flag): the empty block, without the search.
+struct PitBlock {
+    const int32_t *keys;
+    int64_t n, e;
+    int32_t c;
+    __device__ __forceinline__ bool more() const { return e < n && keys[e] == c; }
+};
+__device__ __forceinline__ PitBlock dd_pit_block(const int32_t *__restrict__ keys, int64_t n, int32_t c, bool has = true)
+{
+    return PitBlock{keys, n, has ? dd_lower_bound(keys, n, c) : n, c};
+}
+
 // wave-aggregated append of the cells that became ready (call from control flow that is uniform per wavefront)
 __device__ __forceinline__ void dd_push(const DistArgs &A, bool pred, int32_t cell)
 {
@@ -96,6 +118,218 @@ __device__ __forceinline__ double dd_result(int stat, const DistAcc &S)
     return r;
 }
 
+// ---- a cell's out-edges
+// one regular out-edge: offset of the facet neighbour, weight, whether the graph has the edge
+struct FacetEdge { int di, dj; double w; bool has; };
+// the facet's two neighbours in ascending cell order (a: the lower cell); swapped: a is the facet's SECOND neighbour (weight 1 - p)
+struct Facet { FacetEdge a, b; bool swapped; };
+
+__device__ __forceinline__ Facet dd_facet_sorted(const DistArgs &A, uint32_t cw, double p)
+{
+    const int s = ci_section(cw);
+    const int ai = fe1r(s), aj = fe1c(s), bi = fe2r(s), bj = fe2c(s);       // (once each: the compiler does not merge two calls)
+    Facet f = {{ai, aj, p, (cw & CI_OUT1) != 0}, {bi, bj, 1 - p, (cw & CI_OUT2) != 0}, false};
+    if (bi * A.m + bj < ai * A.m + aj) { const FacetEdge x = f.a; f.a = f.b; f.b = x; f.swapped = true; }
+    return f;
+}
+
+// f(dst, di, dj, w) for every out-edge c -> dst = c + (di, dj) of weight w, in the order every reverse sweep pulls them in:
+// ascending destination, a regular edge before a pit edge to the same cell.  cw: the graph word of c.
+template <class F>
+__device__ __forceinline__ void dd_for_out_edges(const DistArgs &A, int32_t c, uint32_t cw, F f)
+{
+    const int i = c / A.m, j = c - i * A.m;
+    int nr = 0, rdi[2], rdj[2];                         // (one array per field: an array of structs indexed by ir would go to LDS)
+    double rw[2];
+    if (cw & (CI_OUT1 | CI_OUT2)) {
+        const Facet ft = dd_facet_sorted(A, cw, A.prop[c]);
+        if (ft.a.has) { rdi[nr] = ft.a.di; rdj[nr] = ft.a.dj; rw[nr] = ft.a.w; nr++; }
+        if (ft.b.has) { rdi[nr] = ft.b.di; rdj[nr] = ft.b.dj; rw[nr] = ft.b.w; nr++; }
+    }
+    PitBlock b = dd_pit_block(A.pit_src, A.n_pit, c, (cw & CI_PIT_OUT) != 0);
+    for (int ir = 0;;) {
+        const bool hr = ir < nr, hp = b.more();
+        if (!hr && !hp) break;
+        const int32_t rd = hr ? c + rdi[ir] * A.m + rdj[ir] : 0;
+        const int32_t pd = hp ? A.pit_dst[b.e] : 0;
+        if (hr && (!hp || rd <= pd)) { f(rd, rdi[ir], rdj[ir], rw[ir]); ir++; }
+        else { const int pi = pd / A.m; f(pd, pi - i, pd - pi * A.m - j, A.pit_w[b.e]); b.e++; }
+    }
+}
+
+// ---- the frame of a tile visit
+// One workgroup of 256 threads visits one 32 x 32 tile in a pass: it stages values and final flags of tile + halo in LDS, runs
+// rounds to the fixed point with one barrier each, then stores what it finished with the pass number as stamp.  The rules:
+//
+//   stamps    a cell outside the workgroup's hands (the halo, the far end of a pit edge) is final only if its stamp is from an
+//             EARLIER pass (stamp < pass; 0: final from the start, DD_STAMP_OPEN: open).  A stamp of the current pass -- written by
+//             whoever owns the cell, in this launch -- reads as open, so a tile never reads what another workgroup writes in
+//             the same launch and the set a pass finishes is the same in every run.
+//   rounds    a cell is ready in round r only on flags < r: its neighbours became final in an EARLIER round, so what a round
+//             writes -- flags = r, values of cells nobody may read yet -- cannot change what the round reads.  At most 1024
+//             rounds: every round but the last finishes a cell.  The round loops are the sweeps' own (the kernels).
+//   results   leave once, after the rounds (a barrier waits for the stores in flight: one store per round made every round as
+//             long as a trip to memory).
+//   visits    from the second pass on a tile is visited while it has open cells and it or one of its 8 neighbours finished
+//             something in the pass before.  Four words per tile behind the counter block say so: open cells after its last
+//             visit; for each parity of the pass number the last pass of that parity in which it finished something (this pass
+//             writes one word while the workgroups around read the other); cells finished by its visit of the current pass, -1
+//             if it was skipped (summed by k_dd_pass_sum: a counter all tiles add to would serialise them).
+struct TileVisit {
+    bool run;                                           // false: skipped, the workgroup returns (before any barrier)
+    int tile, i0, j0;                                   // the tile's index; row and column of the halo's first cell
+    int32_t *tile_open, *prog_w, *tile_done;
+};
+
+__device__ __forceinline__ TileVisit dd_visit_begin(int32_t *tile_state, int32_t pass, int tiles_x, int tiles_y)
+{
+    const int ntiles = tiles_x * tiles_y;
+    const int32_t *prog_r = tile_state + (1 + ((pass - 1) & 1)) * (int64_t)ntiles;
+    const int tile = blockIdx.x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    TileVisit V = {true, tile, ty * DD_T - 1, tx * DD_T - 1,
+                   tile_state, tile_state + (1 + (pass & 1)) * (int64_t)ntiles, tile_state + 3 * (int64_t)ntiles};
+    if (pass > 1) {                                     // (uniform per workgroup: everything read here is from earlier launches)
+        bool visit = false;
+        if (V.tile_open[tile] > 0)
+            for (int a = -1; a <= 1; a++)
+                for (int b = -1; b <= 1; b++) {
+                    const int yy = ty + a, xx = tx + b;
+                    if (yy >= 0 && yy < tiles_y && xx >= 0 && xx < tiles_x && prog_r[yy * tiles_x + xx] == pass - 1) visit = true;
+                }
+        if (!visit) {
+            if (threadIdx.x == 0) V.tile_done[tile] = -1;
+            V.run = false;
+        }
+    }
+    return V;
+}
+
+// Values and flags of tile + halo: Dl = the value of a final cell, Fl = the round of the visit in which the cell became final
+// (0: before it, DD_FL_OPEN: not yet).  What else the sweep wants of a slot it stages in two steps: load(c) for a cell c on the grid,
+// next to the value's load, and store(t) for every slot t, next to the value's store.  (One callable after the stamp test put its
+// loads behind the value's: three trips to memory per slot where the parent had two, 0.5 % of a forward sweep.)  Clears the
+// visit's two counters; ends with the barrier after which the slots may be read.
+template <class Load, class Store>
+__device__ __forceinline__ void dd_stage(const DistArgs &A, int32_t pass, const TileVisit &V, double *Dl, uint16_t *Fl,
+                                         int32_t &s_done, int32_t &s_open, Load load, Store store)
+{
+    const int32_t *stamp = A.queue;
+    if (threadIdx.x == 0) { s_done = 0; s_open = 0; }
+    for (int t = threadIdx.x; t < DD_H * DD_H; t += 256) {
+        const int li = t / DD_H, lj = t - li * DD_H;
+        const int gi = V.i0 + li, gj = V.j0 + lj;
+        bool fin = false;
+        double d = 0.0;
+        if (gi >= 0 && gi < A.n && gj >= 0 && gj < A.m) {
+            const int32_t c = gi * A.m + gj;
+            fin = stamp[c] < pass;
+            if (fin) d = A.D[c];
+            load(c);
+        }
+        store(t);
+        Dl[t] = d; Fl[t] = fin ? (uint16_t)0 : DD_FL_OPEN;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void dd_stage(const DistArgs &A, int32_t pass, const TileVisit &V, double *Dl, uint16_t *Fl, int32_t &s_done, int32_t &s_open)
+{
+    dd_stage(A, pass, V, Dl, Fl, s_done, s_open, [](int32_t) {}, [](int) {});
+}
+
+// this thread's k-th cell (k = 0..3): row (threadIdx.x / 32) + 8 k of the tile, column threadIdx.x % 32; idx: its LDS slot
+struct CellSlot { int gi, gj, idx; };
+__device__ __forceinline__ CellSlot dd_slot(int k, const TileVisit &V)
+{
+    const int ti = (int)(threadIdx.x >> 5) + 8 * k, tj = (int)(threadIdx.x & 31);
+    return CellSlot{V.i0 + 1 + ti, V.j0 + 1 + tj, (ti + 1) * DD_H + tj + 1};
+}
+__device__ __forceinline__ int32_t dd_slot_cell(const DistArgs &A, const CellSlot &s) { return s.gi * A.m + s.gj; }
+// the cell is on the grid and was open when the visit began: one of those the visit may finish
+__device__ __forceinline__ bool dd_slot_open(const DistArgs &A, const CellSlot &s, const uint16_t *Fl) { return s.gi < A.n && s.gj < A.m && Fl[s.idx] != 0; }
+
+// the k-th of a thread's four per-cell values, selected, not branched on: a wavefront runs an evaluation as often as its busiest
+// lane has ready cells in the round -- usually once -- not once per cell slot
+#define DD_SEL(a, k) ((k) == 0 ? a[0] : (k) == 1 ? a[1] : (k) == 2 ? a[2] : a[3])
+
+// After the rounds: value(k, s) of the cells in `finished` (bit k: the thread's k-th cell, s its slot) goes to cell(k, s) of the
+// result plane with the pass as stamp; then the tile's words.  n_open: how many of the thread's cells were open when the visit
+// began.  (The cell is the kernel's to hand out: one that needs it in its rounds keeps it in a register, and working it out
+// again from the slot cost k_du_tiles three VGPRs; one that does not recomputes it, dd_slot_cell.)
+template <class Cell, class Value>
+__device__ __forceinline__ void dd_visit_end(const DistArgs &A, int32_t pass, const TileVisit &V, int32_t &s_done, int32_t &s_open,
+                                             int n_open, unsigned finished, Cell cell, Value value)
+{
+    int32_t *stamp = A.queue;
+    int n_done = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (finished & (1u << k)) {
+            const CellSlot s = dd_slot(k, V);
+            const int32_t c = cell(k, s);
+            A.D[c] = value(k, s); stamp[c] = pass; n_done++;
+        }
+    if (n_open) atomicAdd(&s_open, n_open - n_done);
+    if (n_done) atomicAdd(&s_done, n_done);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        V.tile_open[V.tile] = s_open;
+        if (s_done) V.prog_w[V.tile] = pass;
+        V.tile_done[V.tile] = s_done;
+    }
+}
+
+// ---- the two kernels every sweep has
+// The cell pattern of a call.  classify(A, c, i, j, cw, value) says whether the cell c = (i, j) with graph word cw starts open;
+// if not, `value` is its final value.  An open cell gets the open pattern and DD_STAMP_OPEN, a final one its value and stamp 0.
+template <class Classify>
+__global__ __launch_bounds__(256) void k_flow_init(DistArgs A, Classify classify)
+{
+    unsigned long long *n_open = reinterpret_cast<unsigned long long *>(A.ctr + DD_NOPEN);
+    __shared__ int32_t s_open;
+    if (threadIdx.x == 0) s_open = 0;
+    __syncthreads();
+    int32_t mine = 0;
+    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
+    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
+        const int j = j0 + (int)threadIdx.x;
+        bool open = false;
+        if (j < A.m) {
+            const int32_t c = i * A.m + j;
+            double v = 0.0;
+            open = classify(A, c, i, j, A.cinfo[c], v);
+            if (open) reinterpret_cast<uint2 *>(A.D)[c] = make_uint2(0u, DD_OPEN_HI);
+            else A.D[c] = v;
+            A.queue[c] = open ? DD_STAMP_OPEN : 0;
+        }
+        mine += open ? 1 : 0;
+    }
+    // one global atomic per workgroup (a word takes ~90 atomics per microsecond: one per wavefront and row was most of this kernel)
+    if (mine) atomicAdd(&s_open, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_open) atomicAdd(n_open, (unsigned long long)s_open);
+}
+
+// One level of the queue: the lane finishes its cell of the window [DD_LO, DD_HI) -- finish(A, v, cw) is its value, all it reads
+// is from earlier launches -- then release(A, v, cw) takes one off the counts that waited for it and appends those that reach
+// zero.  The release runs in control flow that is uniform per wavefront: a lane without a cell passes cw = 0.
+template <class Finish, void (*Release)(const DistArgs &, int32_t, uint32_t)>
+__global__ __launch_bounds__(256) void k_flow_level(DistArgs A, Finish finish)
+{
+    const int64_t lo = A.ctr[DD_LO], hi = A.ctr[DD_HI];
+    for (int64_t base = lo + (int64_t)blockIdx.x * blockDim.x; base < hi; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = base + threadIdx.x;
+        int32_t v = 0;
+        uint32_t cw = 0;
+        if (k < hi) {
+            v = A.queue[k];
+            cw = A.cinfo[v];
+            A.D[v] = finish(A, v, cw);
+        }
+        Release(A, v, cw);
+    }
+}
+
 // cells finished and tiles visited by a pass, from the tiles' own words (-1: not visited)
 __global__ __launch_bounds__(256) void k_dd_pass_sum(const int32_t *__restrict__ tile_done, int ntiles, int32_t *ctr)
 {
@@ -125,7 +359,7 @@ __global__ void k_dd_advance(int32_t *ctr)
     }
 }
 
-// ---- the queue of a REVERSE sweep (flowdist.hip, flowacc_rev.hip): both depend on the graph alone, not on the statistic
+// ---- the queue of a REVERSE sweep (flowdist.hip, flowacc_rev.hip): it depends on the graph alone, not on what is accumulated
 // cell v is final: every open cell with an edge into v has one open out-edge less.  `cw` = graph word of v, 0 for a lane
 // that holds no cell.
 __device__ __forceinline__ void dd_release(const DistArgs &A, int32_t v, uint32_t cw)
@@ -139,8 +373,8 @@ __device__ __forceinline__ void dd_release(const DistArgs &A, int32_t v, uint32_
         dd_push(A, ready, u);
     }
     if (cw & CI_PIT_IN) {
-        for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, v); e < A.n_pit && A.pin_dst[e] == v; e++) {
-            const int32_t u = A.pin_src[e];
+        for (PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, v); b.more(); b.e++) {
+            const int32_t u = A.pin_src[b.e];
             if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
                 const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
                 if (slot < A.qcap) A.queue[slot] = u;
@@ -166,8 +400,8 @@ __global__ __launch_bounds__(256) void k_dd_recount(DistArgs A)
                 if ((cw & CI_OUT1) && dd_is_open(A, c + fe1r(s) * A.m + fe1c(s))) cnt++;
                 if ((cw & CI_OUT2) && dd_is_open(A, c + fe2r(s) * A.m + fe2c(s))) cnt++;
                 if (cw & CI_PIT_OUT)
-                    for (int64_t e = dd_lower_bound(A.pit_src, A.n_pit, c); e < A.n_pit && A.pit_src[e] == c; e++)
-                        if (dd_is_open(A, A.pit_dst[e])) cnt++;
+                    for (PitBlock b = dd_pit_block(A.pit_src, A.n_pit, c); b.more(); b.e++)
+                        if (dd_is_open(A, A.pit_dst[b.e])) cnt++;
                 *dd_count(A, c) = cnt;
                 ready = cnt == 0;
             }
@@ -192,7 +426,33 @@ static dim3 dist_row_grid(const pydem_tile *t)
     return dim3(gx, gy < (unsigned)t->n ? gy : (unsigned)t->n);
 }
 
-// the state both calls share (allocated by the first call of either, freed with the tile) and the argument block over it
+// What every entry point checks of its tile (`what`: the function's name); 0, or the error code with the message set.  In two
+// steps, because the checks of the call's own arguments come between them: there is a tile and its device is current; the tile
+// has a flow graph.
+static int dist_check_tile(pydem_tile *t, const char *what)
+{
+    if (!t) { pydem_set_error("%s: no tile", what); return -2; }
+    HIP_TRY(hipSetDevice(t->device));
+    return 0;
+}
+static int dist_check_graph(pydem_tile *t, const char *what)
+{
+    if (!t->graph_valid || !t->cinfo || !t->prop || !t->have[PYDEM_PROPORTION] || !t->have[PYDEM_ELEV] || !t->spacing_set) {
+        pydem_set_error("%s: no flow graph on this tile (pydem_uca / pydem_build_graph first)", what);
+        return -3;
+    }
+    return 0;
+}
+
+// a plane of the call's own (a mask, a seed) on the device: allocated on first use, freed with the tile
+template <class T>
+static int dist_upload(pydem_tile *t, T **plane, const T *src)
+{
+    PYDEM_TRY(tile_alloc(t, plane, (size_t)t->NN));
+    return tile_plane_copy(t, *plane, const_cast<T *>(src), (size_t)t->NN * sizeof(T), false);
+}
+
+// the state the calls share (allocated by the first call of any, freed with the tile) and the argument block over it
 static int dist_state(pydem_tile *t, DistArgs &A, int kind, int stat)
 {
     const int64_t ntiles = cdiv(t->m, DD_T) * cdiv(t->n, DD_T);
@@ -211,10 +471,10 @@ static int dist_state(pydem_tile *t, DistArgs &A, int kind, int stat)
     return 0;
 }
 
-// The schedule of a call, the same for both directions: the counters, the cell pattern (`init`), tile passes while they pay
+// The schedule of a call, the same for every sweep: the counters, the cell pattern (`init`), tile passes while they pay
 // (`tiles`), the queue for the rest (`recount`, then one `level` launch per level), NaN for what never became ready, the
-// timing and the download.  The four arguments launch the direction's kernels on the tile's stream; default_per_visit: the
-// cells a tile visit has to finish on average for another pass to beat the queue (the switch point of the direction).
+// timing and the download.  The four arguments launch the sweep's kernels on the tile's stream; default_per_visit: the
+// cells a tile visit has to finish on average for another pass to beat the queue (the switch point of the sweep).
 template <class FInit, class FTiles, class FRecount, class FLevel>
 static int dist_schedule(pydem_tile *t, const char *what, int64_t default_per_visit, double *out, double *ms, int64_t *levels,
                          int64_t *n_unresolved, FInit init, FTiles tiles, FRecount recount, FLevel level)
@@ -289,4 +549,18 @@ static int dist_schedule(pydem_tile *t, const char *what, int64_t default_per_vi
     }
     if (out) PYDEM_TRY(tile_plane_copy(t, t->dd_out, out, (size_t)t->NN * 8, true));
     return 0;
+}
+
+// dist_schedule with the launches every sweep makes the same way: the init and the level kernel from the sweep's Classify,
+// Finish and release, its recount kernel over the rows; tiles(grid, pass, tiles_x, tiles_y, tile_state) launches its tile pass.
+template <void (*Release)(const DistArgs &, int32_t, uint32_t), class Classify, class Finish, class FTiles>
+static int dist_sweep(pydem_tile *t, const char *what, int64_t default_per_visit, const DistArgs &A, Classify classify, Finish finish,
+                      void (*recount)(DistArgs), FTiles tiles, double *out, double *ms, int64_t *levels, int64_t *n_unresolved)
+{
+    const dim3 rows = dist_row_grid(t);
+    return dist_schedule(t, what, default_per_visit, out, ms, levels, n_unresolved,
+        [&] { hipLaunchKernelGGL(k_flow_init<Classify>, rows, dim3(256), 0, t->stream, A, classify); },
+        [&](int pass, int tiles_x, int tiles_y, int32_t *tile_state) { tiles(dim3((unsigned)(tiles_x * tiles_y)), (int32_t)pass, tiles_x, tiles_y, tile_state); },
+        [&] { hipLaunchKernelGGL(recount, rows, dim3(256), 0, t->stream, A); },
+        [&](int grid) { hipLaunchKernelGGL((k_flow_level<Finish, Release>), dim3(grid), dim3(256), 0, t->stream, A, finish); });
 }

@@ -6,18 +6,15 @@
 // out-neighbours in a fixed order (ascending destination, a regular edge before a pit edge to the same cell), so there are
 // no floating-point atomics and a value does not depend on the schedule that produced it.  An open cell's slot of the result
 // plane holds {count, DD_OPEN_HI}: a NaN no arithmetic here produces (final NaNs are stored canonical), so "final" needs no
-// plane of its own and a cell that never becomes ready reads as NaN.  k_dd_init writes 0 to the targets, NaN to the cells
-// without an out-edge, the open pattern to the others, and a pass stamp per cell (0 = final, INT_MAX = open).  Two schedules:
+// plane of its own and a cell that never becomes ready reads as NaN.  The init kernel (DownClassify) writes 0 to the targets,
+// NaN to the cells without an out-edge, the open pattern to the others, and a pass stamp per cell (0 = final, INT_MAX = open).
+// Two schedules:
 //
-//   tile passes (k_dd_tiles), like the forward sweep's: one workgroup per 32 x 32 tile stages final flags and values of tile
-//   + halo in LDS and runs rounds to the fixed point -- a cell is ready when the one or two cells its facet points at are
-//   final -- then stores what it finished with the pass number as stamp.  A cell outside the tile (the halo, a pit's drains)
-//   is final only if its stamp is from an EARLIER pass, so a tile never reads what another workgroup writes in the same launch
-//   and the set a pass finishes is the same in every run.  A path advances one tile per pass; a tile is visited while it has
-//   open cells and it or one of its 8 neighbours finished something in the pass before.  The host looks at two counters per
-//   pass and stops the passes when a visit finishes fewer cells than it costs (DD_MIN_PER_VISIT).
+//   tile passes (k_dd_tiles), like the forward sweep's, in the visit frame of flowdist.h: a cell is ready when the one or two
+//   cells its facet points at are final.  A path advances one tile per pass.  The host looks at two counters per pass and
+//   stops the passes when a visit finishes fewer cells than it costs (DD_MIN_PER_VISIT).
 //
-//   the queue (k_dd_recount, k_dd_level) takes what is left, whatever it is -- the passes are an accelerator, not needed for
+//   the queue (k_dd_recount, k_flow_level) takes what is left, whatever it is -- the passes are an accelerator, not needed for
 //   the result: reverse Kahn.  k_dd_recount writes the number of open out-neighbours into every open cell's slot and
 //   appends the cells with none; a level is one launch over the cells the previous one appended: the lane finishes its
 //   cell, then takes one off the counts of the open cells upstream of it (in-mask bits 0-7 of the graph word, pit in-list;
@@ -30,8 +27,8 @@
 // stamps of the passes, then the queue -- every cell enters it at most once, so the segments of all levels fit one after the
 // other), the mask of a call with mask targets (1 B per cell) and four words per tile.  Reads the graph words, proportion,
 // elevation, uca (threshold targets), the pit lists and the spacing; writes nothing else of the tile.
-// What the forward sweep of the same statistic (flowdist_up.hip, pydem_dist_up) shares with this one -- the state, the encoding,
-// the accumulator, the small kernels and the host's schedule -- is in flowdist.h.
+// Everything here that is not this sweep's own -- the state, the encoding, the out-edge order, the visit frame, the init and
+// level kernels, the host's schedule -- is in flowdist.h, shared with flowdist_up.hip and flowacc_rev.hip.
 #include "flowdist.h"
 
 namespace {
@@ -42,114 +39,44 @@ __device__ __forceinline__ void dd_edge(const DistArgs &A, DistAcc &S, int32_t d
     dd_add(S, w, A.D[dst] + dd_cost(A.kind, di, dj, dx, dy, zc, A.kind != 0 ? A.elev[dst] : 0.0));
 }
 
-// the value of an open cell whose out-neighbours are all final
-__device__ __forceinline__ double dd_finish(const DistArgs &A, int32_t c, uint32_t cw)
-{
-    const int i = c / A.m, j = c - i * A.m;
-    const double dx = A.dX2[i], dy = A.dY2[i];
-    const double zc = A.kind != 0 ? A.elev[c] : 0.0;
-    // regular edges in ascending destination order
-    int nr = 0;
-    int rdi[2], rdj[2]; double rw[2];
-    if (cw & (CI_OUT1 | CI_OUT2)) {
-        const int s = ci_section(cw);
-        const double p = A.prop[c];
-        if (cw & CI_OUT1) { rdi[nr] = fe1r(s); rdj[nr] = fe1c(s); rw[nr] = p; nr++; }
-        if (cw & CI_OUT2) { rdi[nr] = fe2r(s); rdj[nr] = fe2c(s); rw[nr] = 1 - p; nr++; }
-        if (nr == 2 && rdi[1] * A.m + rdj[1] < rdi[0] * A.m + rdj[0]) {
-            const int a = rdi[0], b = rdj[0]; const double w = rw[0];
-            rdi[0] = rdi[1]; rdj[0] = rdj[1]; rw[0] = rw[1];
-            rdi[1] = a; rdj[1] = b; rw[1] = w;
-        }
+// the value of an open cell whose out-neighbours are all final (the level kernel's Finish)
+struct DownFinish {
+    __device__ __forceinline__ double operator()(const DistArgs &A, int32_t c, uint32_t cw) const
+    {
+        const int i = c / A.m;
+        const double dx = A.dX2[i], dy = A.dY2[i];
+        const double zc = A.kind != 0 ? A.elev[c] : 0.0;
+        DistAcc S;
+        dd_for_out_edges(A, c, cw, [&](int32_t dst, int di, int dj, double w) { dd_edge(A, S, dst, di, dj, w, dx, dy, zc); });
+        return dd_result(A.stat, S);
     }
-    DistAcc S;
-    int64_t e = A.n_pit;
-    if (cw & CI_PIT_OUT) e = dd_lower_bound(A.pit_src, A.n_pit, c);
-    int ir = 0;
-    for (;;) {
-        const bool hr = ir < nr, hp = e < A.n_pit && A.pit_src[e] == c;
-        if (!hr && !hp) break;
-        const int32_t rd = hr ? c + rdi[ir] * A.m + rdj[ir] : 0;
-        const int32_t pd = hp ? A.pit_dst[e] : 0;
-        if (hr && (!hp || rd <= pd)) { dd_edge(A, S, rd, rdi[ir], rdj[ir], rw[ir], dx, dy, zc); ir++; }
-        else { const int pi = pd / A.m; dd_edge(A, S, pd, pi - i, pd - pi * A.m - j, A.pit_w[e], dx, dy, zc); e++; }
-    }
-    return dd_result(A.stat, S);
-}
+};
 
-// targets (the mask, or uca >= threshold), cells without an out-edge, the open pattern and the stamps of the others
-__global__ __launch_bounds__(256) void k_dd_init(DistArgs A, const double *__restrict__ uca, double threshold)
-{
-    unsigned long long *n_open = reinterpret_cast<unsigned long long *>(A.ctr + DD_NOPEN);
-    __shared__ int32_t s_open;
-    if (threadIdx.x == 0) s_open = 0;
-    __syncthreads();
-    int32_t mine = 0;
-    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
-    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
-        const int j = j0 + (int)threadIdx.x;
-        bool open = false;
-        if (j < A.m) {
-            const int32_t c = i * A.m + j;
-            const uint32_t cw = A.cinfo[c];
-            const bool tg = uca ? uca[c] >= threshold : A.mask[c] != 0;      // (NaN is never a target)
-            open = !tg && (cw & (CI_OUT1 | CI_OUT2 | CI_PIT_OUT));
-            if (open) reinterpret_cast<uint2 *>(A.D)[c] = make_uint2(0u, DD_OPEN_HI);
-            else A.D[c] = tg ? 0.0 : dd_nan();
-            A.queue[c] = open ? DD_STAMP_OPEN : 0;
-        }
-        mine += open ? 1 : 0;
+// targets (the mask, or uca >= threshold): 0; cells without an out-edge: NaN; the others are open
+struct DownClassify {
+    const double *uca;
+    double threshold;
+    __device__ __forceinline__ bool operator()(const DistArgs &A, int32_t c, int, int, uint32_t cw, double &value) const
+    {
+        const bool tg = uca ? uca[c] >= threshold : A.mask[c] != 0;      // (NaN is never a target)
+        value = tg ? 0.0 : dd_nan();
+        return !tg && (cw & (CI_OUT1 | CI_OUT2 | CI_PIT_OUT));
     }
-    // one global atomic per workgroup (a word takes ~90 atomics per microsecond: one per wavefront and row was most of this kernel)
-    if (mine) atomicAdd(&s_open, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_open) atomicAdd(n_open, (unsigned long long)s_open);
-}
+};
 
-// ---- tile passes
-// One workgroup, one tile, four cells per thread.  A cell with regular out-edges waits for the flags of its one or two
-// destinations in LDS; a drained pit (pit edges only) is finished when it is loaded if all its drains are final from an
-// earlier pass; a cell with both kinds of edges is left to the queue.
+// ---- tile passes (the frame and its rules: flowdist.h)
+// A cell with regular out-edges waits for the flags of its one or two destinations in LDS; a drained pit (pit edges only) is
+// finished when it is loaded if all its drains are final from an earlier pass; a cell with both kinds of edges is left to the
+// queue.
 __global__ __launch_bounds__(256) void k_dd_tiles(DistArgs A, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state)
 {
     __shared__ double Dl[DD_H * DD_H];
-    __shared__ uint16_t Fl[DD_H * DD_H];        // round of the visit in which the cell became final (0: before it, DD_FL_OPEN: not yet)
+    __shared__ uint16_t Fl[DD_H * DD_H];
     __shared__ int32_t s_done, s_open;
-    const int ntiles = tiles_x * tiles_y;
-    int32_t *tile_open = tile_state, *prog_w = tile_state + (1 + (pass & 1)) * (int64_t)ntiles, *tile_done = tile_state + 3 * (int64_t)ntiles;
-    const int32_t *prog_r = tile_state + (1 + ((pass - 1) & 1)) * (int64_t)ntiles;
-    const int tile = blockIdx.x;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    if (pass > 1) {                                     // (uniform per workgroup: everything read here is from earlier launches)
-        bool visit = false;
-        if (tile_open[tile] > 0)
-            for (int a = -1; a <= 1; a++)
-                for (int b = -1; b <= 1; b++) {
-                    const int yy = ty + a, xx = tx + b;
-                    if (yy >= 0 && yy < tiles_y && xx >= 0 && xx < tiles_x && prog_r[yy * tiles_x + xx] == pass - 1) visit = true;
-                }
-        if (!visit) {
-            if (threadIdx.x == 0) tile_done[tile] = -1;
-            return;
-        }
-    }
-    int32_t *stamp = A.queue;
-    const int i0 = ty * DD_T - 1, j0 = tx * DD_T - 1;
-    if (threadIdx.x == 0) { s_done = 0; s_open = 0; }
-    for (int t = threadIdx.x; t < DD_H * DD_H; t += 256) {
-        const int li = t / DD_H, lj = t - li * DD_H;
-        const int gi = i0 + li, gj = j0 + lj;
-        bool fin = false;
-        double d = 0.0;
-        if (gi >= 0 && gi < A.n && gj >= 0 && gj < A.m) {
-            const int32_t c = gi * A.m + gj;
-            fin = stamp[c] < pass;                      // (a stamp of this pass, written by whoever owns the cell, reads as open)
-            if (fin) d = A.D[c];
-        }
-        Dl[t] = d; Fl[t] = fin ? (uint16_t)0 : DD_FL_OPEN;
-    }
-    __syncthreads();
-    // this thread's cells: k-th cell = row (threadIdx.x / 32) + 8 k of the tile, column threadIdx.x % 32
+    const TileVisit V = dd_visit_begin(tile_state, pass, tiles_x, tiles_y);
+    if (!V.run) return;
+    dd_stage(A, pass, V, Dl, Fl, s_done, s_open);
+    const int32_t *stamp = A.queue;
     int32_t cell[4];
     int idx[4], d1[4], d2[4];
     double w1[4], w2[4], c1[4], c2[4], val[4];
@@ -157,55 +84,37 @@ __global__ __launch_bounds__(256) void k_dd_tiles(DistArgs A, int32_t pass, int 
     int n_open = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int ti = (int)(threadIdx.x >> 5) + 8 * k, tj = (int)(threadIdx.x & 31);
-        const int gi = i0 + 1 + ti, gj = j0 + 1 + tj;
-        idx[k] = (ti + 1) * DD_H + tj + 1;
-        open[k] = false; pend[k] = false; d1[k] = d2[k] = -1; w1[k] = w2[k] = c1[k] = c2[k] = val[k] = 0.0;
-        cell[k] = 0;
-        if (gi >= A.n || gj >= A.m || Fl[idx[k]] == 0) continue;
-        const int32_t c = gi * A.m + gj;
-        cell[k] = c;
+        const CellSlot sl = dd_slot(k, V);
+        idx[k] = sl.idx;
+        cell[k] = 0; open[k] = false; pend[k] = false; d1[k] = d2[k] = -1; w1[k] = w2[k] = c1[k] = c2[k] = val[k] = 0.0;
+        if (!dd_slot_open(A, sl, Fl)) continue;
+        const int32_t c = cell[k] = dd_slot_cell(A, sl);
         n_open++;
         const uint32_t cw = A.cinfo[c];
         const bool regular = (cw & (CI_OUT1 | CI_OUT2)) != 0;
         if (regular && (cw & CI_PIT_OUT)) continue;
-        const double dx = A.dX2[gi], dy = A.dY2[gi];
+        const double dx = A.dX2[sl.gi], dy = A.dY2[sl.gi];
         const double zc = A.kind != 0 ? A.elev[c] : 0.0;
         if (!regular) {
             DistAcc S;
             bool settled = true;
-            for (int64_t e = dd_lower_bound(A.pit_src, A.n_pit, c); e < A.n_pit && A.pit_src[e] == c; e++) {
-                const int32_t pd = A.pit_dst[e];
+            for (PitBlock b = dd_pit_block(A.pit_src, A.n_pit, c); b.more(); b.e++) {
+                const int32_t pd = A.pit_dst[b.e];
                 settled = settled && stamp[pd] < pass;
                 const int pi = pd / A.m;
-                dd_edge(A, S, pd, pi - gi, pd - pi * A.m - gj, A.pit_w[e], dx, dy, zc);
+                dd_edge(A, S, pd, pi - sl.gi, pd - pi * A.m - sl.gj, A.pit_w[b.e], dx, dy, zc);
             }
             if (settled) { pend[k] = true; val[k] = dd_result(A.stat, S); open[k] = true; }
             continue;
         }
-        const int s = ci_section(cw);
-        const double p = A.prop[c];
-        // the facet's two neighbours in ascending cell order
-        int ai = fe1r(s), aj = fe1c(s), bi = fe2r(s), bj = fe2c(s);
-        double wa = p, wb = 1 - p;
-        bool ha = (cw & CI_OUT1) != 0, hb = (cw & CI_OUT2) != 0;
-        if (bi * A.m + bj < ai * A.m + aj) {
-            const int x = ai, y = aj; ai = bi; aj = bj; bi = x; bj = y;
-            const double w = wa; wa = wb; wb = w;
-            const bool h = ha; ha = hb; hb = h;
-        }
-        if (ha) { d1[k] = idx[k] + ai * DD_H + aj; w1[k] = wa; c1[k] = dd_cost(A.kind, ai, aj, dx, dy, zc, A.kind != 0 ? A.elev[c + ai * A.m + aj] : 0.0); }
-        if (hb) { d2[k] = idx[k] + bi * DD_H + bj; w2[k] = wb; c2[k] = dd_cost(A.kind, bi, bj, dx, dy, zc, A.kind != 0 ? A.elev[c + bi * A.m + bj] : 0.0); }
+        const Facet f = dd_facet_sorted(A, cw, A.prop[c]);
+        if (f.a.has) { d1[k] = idx[k] + f.a.di * DD_H + f.a.dj; w1[k] = f.a.w; c1[k] = dd_cost(A.kind, f.a.di, f.a.dj, dx, dy, zc, A.kind != 0 ? A.elev[c + f.a.di * A.m + f.a.dj] : 0.0); }
+        if (f.b.has) { d2[k] = idx[k] + f.b.di * DD_H + f.b.dj; w2[k] = f.b.w; c2[k] = dd_cost(A.kind, f.b.di, f.b.dj, dx, dy, zc, A.kind != 0 ? A.elev[c + f.b.di * A.m + f.b.dj] : 0.0); }
         open[k] = true;
     }
-    // Rounds to the fixed point, one barrier each: a cell is ready in round r when its destinations became final in an
-    // EARLIER round (flag < r), so what this round writes -- flags = r, values of cells nobody may read yet -- cannot change
-    // what this round reads.  A wavefront runs the evaluation (a division, the NaN rule) as often as its busiest lane has
-    // ready cells in the round -- usually once -- not once per cell slot: the slot's operands are selected, not branched on.
-#define DD_SEL(a, k) ((k) == 0 ? a[0] : (k) == 1 ? a[1] : (k) == 2 ? a[2] : a[3])
-    int n_done = 0;
+    // the rounds (their invariant: flowdist.h); the evaluation -- a division, the NaN rule -- runs on selected operands (DD_SEL)
     unsigned finished = 0;
-    for (unsigned r = 1;; r++) {                        // (at most 1024 rounds: every round but the last finishes a cell)
+    for (unsigned r = 1;; r++) {
         unsigned fresh = 0, todo = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -233,80 +142,32 @@ __global__ __launch_bounds__(256) void k_dd_tiles(DistArgs A, int32_t pass, int 
             }
         if (!__syncthreads_or(fresh != 0)) break;
     }
-    // results leave once, after the rounds (a barrier waits for the stores in flight: one store per round made every round
-    // as long as a trip to memory)
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        if (finished & (1u << k)) { A.D[cell[k]] = val[k]; stamp[cell[k]] = pass; n_done++; }
-#undef DD_SEL
-    if (n_open) atomicAdd(&s_open, n_open - n_done);
-    if (n_done) atomicAdd(&s_done, n_done);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        tile_open[tile] = s_open;
-        if (s_done) prog_w[tile] = pass;
-        tile_done[tile] = s_done;                       // (summed by k_dd_pass_sum: a counter all tiles add to would serialise them)
-    }
-}
-
-// ---- queue
-// (k_dd_recount and dd_release depend on the graph alone: flowdist.h, shared with flowacc_rev.hip)
-__global__ __launch_bounds__(256) void k_dd_level(DistArgs A)
-{
-    const int64_t lo = A.ctr[DD_LO], hi = A.ctr[DD_HI];
-    for (int64_t base = lo + (int64_t)blockIdx.x * blockDim.x; base < hi; base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t k = base + threadIdx.x;
-        int32_t v = 0;
-        uint32_t cw = 0;
-        if (k < hi) {
-            v = A.queue[k];
-            cw = A.cinfo[v];
-            A.D[v] = dd_finish(A, v, cw);
-        }
-        dd_release(A, v, cw);
-    }
+    dd_visit_end(A, pass, V, s_done, s_open, n_open, finished, [&](int k, const CellSlot &) { return cell[k]; },
+                 [&](int k, const CellSlot &) { return val[k]; });
 }
 
 }  // namespace
 
-static int stage_dist_down(pydem_tile *t, int kind, int stat, const uint8_t *target, double threshold, double *out, double *ms,
-                           int64_t *levels, int64_t *n_unresolved)
-{
-    if (target) {
-        PYDEM_TRY(tile_alloc(t, &t->dd_mask, (size_t)t->NN));
-        PYDEM_TRY(tile_plane_copy(t, t->dd_mask, const_cast<uint8_t *>(target), (size_t)t->NN, false));
-    }
-
-    DistArgs A;
-    PYDEM_TRY(dist_state(t, A, kind, stat));
-    const dim3 grid2 = dist_row_grid(t);
-    const double *uca = target ? (const double *)nullptr : (const double *)t->uca;
-    return dist_schedule(t, "dist_down", DD_MIN_PER_VISIT, out, ms, levels, n_unresolved,
-        [&] { hipLaunchKernelGGL(k_dd_init, grid2, dim3(256), 0, t->stream, A, uca, threshold); },
-        [&](int pass, int tiles_x, int tiles_y, int32_t *tile_state) {
-            hipLaunchKernelGGL(k_dd_tiles, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, t->stream, A, (int32_t)pass, tiles_x, tiles_y, tile_state);
-        },
-        [&] { hipLaunchKernelGGL(k_dd_recount, grid2, dim3(256), 0, t->stream, A); },
-        [&](int grid) { hipLaunchKernelGGL(k_dd_level, dim3(grid), dim3(256), 0, t->stream, A); });
-}
-
 extern "C" int pydem_dist_down(pydem_tile *t, int kind, int stat, const uint8_t *target, double uca_threshold, double *out, double *ms,
                                int64_t *levels, int64_t *n_unresolved)
 {
-    if (!t) { pydem_set_error("pydem_dist_down: no tile"); return -2; }
-    HIP_TRY(hipSetDevice(t->device));
+    PYDEM_TRY(dist_check_tile(t, "pydem_dist_down"));
     if (kind < 0 || kind > 2 || stat < 0 || stat > 2) { pydem_set_error("pydem_dist_down: kind %d / stat %d out of range (0..2)", kind, stat); return -2; }
     if (!target && !(uca_threshold >= 0.0 && uca_threshold < INFINITY)) {
         pydem_set_error("pydem_dist_down: uca_threshold must be finite and >= 0 when no target mask is given (got %g)", uca_threshold);
         return -2;
     }
-    if (!t->graph_valid || !t->cinfo || !t->prop || !t->have[PYDEM_PROPORTION] || !t->have[PYDEM_ELEV] || !t->spacing_set) {
-        pydem_set_error("pydem_dist_down: no flow graph on this tile (pydem_uca / pydem_build_graph first)");
-        return -3;
-    }
-    if (!target) {
+    PYDEM_TRY(dist_check_graph(t, "pydem_dist_down"));
+    if (target) PYDEM_TRY(dist_upload(t, &t->dd_mask, target));
+    else {
         if (!t->uca || !t->have[PYDEM_UCA]) { pydem_set_error("pydem_dist_down: uca_threshold needs the tile's uca (pydem_uca first)"); return -3; }
         PYDEM_TRY(stage_edge_flush(t));         // incremental edge rounds: the areas the threshold reads are settled first
     }
-    return stage_dist_down(t, kind, stat, target, uca_threshold, out, ms, levels, n_unresolved);
+    DistArgs A;
+    PYDEM_TRY(dist_state(t, A, kind, stat));
+    const DownClassify targets = {target ? (const double *)nullptr : (const double *)t->uca, uca_threshold};
+    return dist_sweep<dd_release>(t, "dist_down", DD_MIN_PER_VISIT, A, targets, DownFinish{}, k_dd_recount,
+        [&](dim3 grid, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state) {
+            hipLaunchKernelGGL(k_dd_tiles, grid, dim3(256), 0, t->stream, A, pass, tiles_x, tiles_y, tile_state);
+        }, out, ms, levels, n_unresolved);
 }

@@ -7,28 +7,27 @@
 // floating-point atomics and a value does not depend on the schedule that produced it.  The in-neighbours of a cell are bits
 // 0-7 of its graph word (NW N NE W E SW S SE, which is ascending cell order) and its block of the pit in-list; the weight of
 // a regular in-edge from u is p[u] when the cell is u's first (cardinal) facet neighbour and 1 - p[u] when it is the second
-// (diagonal) one; the cost is dd_cost of flowdist.h with u as the source.  State, encoding of an open cell, counters, switches
-// and the host's schedule are those of pydem_dist_down (flowdist.h): a call overwrites the other's device result.
+// (diagonal) one; the cost is dd_cost with u as the source.  State, encoding, counters, switches, the frame of a tile visit,
+// the init and level kernels and the host's schedule are the engine's (flowdist.h): a call overwrites the other sweeps' result.
 //
-//   k_du_init: NaN where the elevation is NaN and, under edge_nan, on the tile's border and beside a NaN elevation; 0 where
-//   nothing flows in; the open pattern and the stamp elsewhere.
+//   the init kernel (UpClassify): NaN where the elevation is NaN and, under edge_nan, on the tile's border and beside a NaN
+//   elevation; 0 where nothing flows in; the open pattern and the stamp elsewhere.
 //
-//   tile passes (k_du_tiles): one workgroup per 32 x 32 tile, four cells per thread, rounds to the fixed point in LDS with one
-//   barrier each.  A cell has up to eight regular in-edges (the reverse sweep: two out-edges), so their weights and costs do
-//   not fit in registers next to four cells' state; what is staged instead is what they are made of, for tile + halo:
+//   tile passes (k_du_tiles).  A cell has up to eight regular in-edges (the reverse sweep: two out-edges), so their weights and
+//   costs do not fit in registers next to four cells' state; what is staged instead is what they are made of, for tile + halo:
 //   value (8 B), proportion (8 B), elevation (8 B, not loaded for kind h), the round flag (2 B) and the spacing of the 34
 //   rows -- 30.9 KB, which would let five workgroups share a CU's 160 KB; the 158 VGPRs of the inlined evaluation (eight
-//   edges, hypot) allow three (3 wavefronts per SIMD, no scratch).  A cell's weights and costs are computed when it is finished, from LDS alone: once per cell
-//   and call, where operands computed at load time would be computed again at every visit of the tile that leaves the cell
-//   open, and no round waits for global memory.  The exception is a cell with pit in-edges (a drain: about one per pit): it
-//   is opened only when all its pits are final from an earlier pass, and its lane then reads their values and list entries
-//   from global memory in the round that finishes it.  A cell outside the tile is final only if its stamp is from an EARLIER
-//   pass; results and stamps are stored once, after the rounds; one counter update per workgroup.
+//   edges, hypot) allow three (3 wavefronts per SIMD, no scratch).  A cell's weights and costs are computed when it is
+//   finished, from LDS alone: once per cell and call, where operands computed at load time would be computed again at every
+//   visit of the tile that leaves the cell open, and no round waits for global memory.  The exception is a cell with pit
+//   in-edges (a drain: about one per pit): it is opened only when all its pits are final from an earlier pass, and its lane
+//   then reads their values and list entries from global memory in the round that finishes it.
 //
-//   the queue (k_du_recount, k_du_level): plain Kahn.  k_du_recount writes the number of open in-neighbours into every open
-//   cell's slot and appends the cells with none; a level finishes the cells the previous one appended, then takes one off the
-//   counts of the open cells its one or two regular out-edges and its pit out-edges lead to (integer atomics), and the lane
-//   whose decrement is the last appends that cell.  A value is always written in a launch before the one that reads it.
+//   the queue (k_du_recount, k_flow_level with du_release): plain Kahn.  k_du_recount writes the number of open in-neighbours
+//   into every open cell's slot and appends the cells with none; a level finishes the cells the previous one appended, then
+//   takes one off the counts of the open cells its one or two regular out-edges and its pit out-edges lead to (integer
+//   atomics), and the lane whose decrement is the last appends that cell.  A value is always written in a launch before the
+//   one that reads it.
 #include "flowdist.h"
 
 namespace {
@@ -47,8 +46,7 @@ template <class Reg>
 __device__ __forceinline__ double du_gather(const DistArgs &A, int32_t c, uint32_t cw, int i, int j, double zc, Reg reg)
 {
     DistAcc S;
-    int64_t e = A.n_pit;
-    if (cw & CI_PIT_IN) e = dd_lower_bound(A.pin_dst, A.n_pit, c);
+    PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, c, (cw & CI_PIT_IN) != 0);
     auto pit = [&](int64_t k) {
         const int32_t u = A.pin_src[k];
         const int ui = u / A.m, uj = u - ui * A.m;
@@ -58,99 +56,54 @@ __device__ __forceinline__ double du_gather(const DistArgs &A, int32_t c, uint32
     for (int d = 0; d < 8; d++) {
         if (!(cw & (1u << d))) continue;
         const int32_t u = c + NB_DI[d] * A.m + NB_DJ[d];
-        for (; e < A.n_pit && A.pin_dst[e] == c && A.pin_src[e] < u; e++) pit(e);
+        for (; b.more() && A.pin_src[b.e] < u; b.e++) pit(b.e);
         double p, du, zu, dx, dy;
         reg(d, u, p, du, zu, dx, dy);
         dd_add(S, du_cardinal(d) ? p : 1 - p, du + dd_cost(A.kind, -NB_DI[d], -NB_DJ[d], dx, dy, zu, zc));
     }
-    for (; e < A.n_pit && A.pin_dst[e] == c; e++) pit(e);
+    for (; b.more(); b.e++) pit(b.e);
     return dd_result(A.stat, S);
 }
 
-__global__ __launch_bounds__(256) void k_du_init(DistArgs A, int edge_nan)
-{
-    unsigned long long *n_open = reinterpret_cast<unsigned long long *>(A.ctr + DD_NOPEN);
-    __shared__ int32_t s_open;
-    if (threadIdx.x == 0) s_open = 0;
-    __syncthreads();
-    int32_t mine = 0;
-    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
-    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
-        const int j = j0 + (int)threadIdx.x;
-        bool open = false;
-        if (j < A.m) {
-            const int32_t c = i * A.m + j;
-            const uint32_t cw = A.cinfo[c];
-            const double z = A.elev[c];
-            bool nanv = z != z;
-            if (edge_nan && !nanv) {
-                nanv = i == 0 || i == A.n - 1 || j == 0 || j == A.m - 1;
-                if (!nanv) {
+// NaN by the elevation and the edge rule; 0 where nothing flows in; the others are open
+struct UpClassify {
+    int edge_nan;
+    __device__ __forceinline__ bool operator()(const DistArgs &A, int32_t c, int i, int j, uint32_t cw, double &value) const
+    {
+        const double z = A.elev[c];
+        bool nanv = z != z;
+        if (edge_nan && !nanv) {
+            nanv = i == 0 || i == A.n - 1 || j == 0 || j == A.m - 1;
+            if (!nanv) {
 #pragma unroll
-                    for (int d = 0; d < 8; d++) { const double zn = A.elev[c + NB_DI[d] * A.m + NB_DJ[d]]; nanv = nanv || zn != zn; }
-                }
+                for (int d = 0; d < 8; d++) { const double zn = A.elev[c + NB_DI[d] * A.m + NB_DJ[d]]; nanv = nanv || zn != zn; }
             }
-            open = !nanv && (cw & (0xFFu | CI_PIT_IN));
-            if (open) reinterpret_cast<uint2 *>(A.D)[c] = make_uint2(0u, DD_OPEN_HI);
-            else A.D[c] = nanv ? dd_nan() : 0.0;
-            A.queue[c] = open ? DD_STAMP_OPEN : 0;
         }
-        mine += open ? 1 : 0;
+        value = nanv ? dd_nan() : 0.0;
+        return !nanv && (cw & (0xFFu | CI_PIT_IN));
     }
-    if (mine) atomicAdd(&s_open, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_open) atomicAdd(n_open, (unsigned long long)s_open);
-}
+};
 
-// ---- tile passes
+// ---- tile passes (the frame and its rules: flowdist.h)
 __global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state)
 {
     __shared__ double Dl[DD_H * DD_H], Pl[DD_H * DD_H], El[DD_H * DD_H];
     __shared__ double Xl[DD_H], Yl[DD_H];
-    __shared__ uint16_t Fl[DD_H * DD_H];        // round of the visit in which the cell became final (0: before it, DD_FL_OPEN: not yet)
+    __shared__ uint16_t Fl[DD_H * DD_H];
     __shared__ int32_t s_done, s_open;
-    const int ntiles = tiles_x * tiles_y;
-    int32_t *tile_open = tile_state, *prog_w = tile_state + (1 + (pass & 1)) * (int64_t)ntiles, *tile_done = tile_state + 3 * (int64_t)ntiles;
-    const int32_t *prog_r = tile_state + (1 + ((pass - 1) & 1)) * (int64_t)ntiles;
-    const int tile = blockIdx.x;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    if (pass > 1) {                                     // (uniform per workgroup: everything read here is from earlier launches)
-        bool visit = false;
-        if (tile_open[tile] > 0)
-            for (int a = -1; a <= 1; a++)
-                for (int b = -1; b <= 1; b++) {
-                    const int yy = ty + a, xx = tx + b;
-                    if (yy >= 0 && yy < tiles_y && xx >= 0 && xx < tiles_x && prog_r[yy * tiles_x + xx] == pass - 1) visit = true;
-                }
-        if (!visit) {
-            if (threadIdx.x == 0) tile_done[tile] = -1;
-            return;
-        }
-    }
-    int32_t *stamp = A.queue;
-    const int i0 = ty * DD_T - 1, j0 = tx * DD_T - 1;
-    if (threadIdx.x == 0) { s_done = 0; s_open = 0; }
+    const TileVisit V = dd_visit_begin(tile_state, pass, tiles_x, tiles_y);
+    if (!V.run) return;
+    const int i0 = V.i0, j0 = V.j0;
     if (threadIdx.x < DD_H) {
         const int gi = i0 + (int)threadIdx.x;
         const bool in = gi >= 0 && gi < A.n;
         Xl[threadIdx.x] = in ? A.dX2[gi] : 0.0; Yl[threadIdx.x] = in ? A.dY2[gi] : 0.0;
     }
-    for (int t = threadIdx.x; t < DD_H * DD_H; t += 256) {
-        const int li = t / DD_H, lj = t - li * DD_H;
-        const int gi = i0 + li, gj = j0 + lj;
-        bool fin = false;
-        double d = 0.0, p = 0.0, z = 0.0;
-        if (gi >= 0 && gi < A.n && gj >= 0 && gj < A.m) {
-            const int32_t c = gi * A.m + gj;
-            fin = stamp[c] < pass;                      // (a stamp of this pass, written by whoever owns the cell, reads as open)
-            if (fin) d = A.D[c];
-            p = A.prop[c];
-            if (A.kind != 0) z = A.elev[c];
-        }
-        Dl[t] = d; Pl[t] = p; El[t] = z; Fl[t] = fin ? (uint16_t)0 : DD_FL_OPEN;
-    }
-    __syncthreads();
-    // this thread's cells: k-th cell = row (threadIdx.x / 32) + 8 k of the tile, column threadIdx.x % 32
+    double p = 0.0, z = 0.0;                            // proportion and elevation of the slot being staged (0 off the grid)
+    dd_stage(A, pass, V, Dl, Fl, s_done, s_open,
+             [&](int32_t c) { p = A.prop[c]; if (A.kind != 0) z = A.elev[c]; },
+             [&](int t) { Pl[t] = p; El[t] = z; p = z = 0.0; });
+    const int32_t *stamp = A.queue;
     int32_t cell[4];
     int idx[4];
     uint32_t word[4], rem[4];
@@ -159,29 +112,25 @@ __global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int 
     int n_open = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int ti = (int)(threadIdx.x >> 5) + 8 * k, tj = (int)(threadIdx.x & 31);
-        const int gi = i0 + 1 + ti, gj = j0 + 1 + tj;
-        idx[k] = (ti + 1) * DD_H + tj + 1;
+        const CellSlot sl = dd_slot(k, V);
+        idx[k] = sl.idx;
         open[k] = false; cell[k] = 0; word[k] = 0; rem[k] = 0; val[k] = 0.0;
-        if (gi >= A.n || gj >= A.m || Fl[idx[k]] == 0) continue;
-        const int32_t c = gi * A.m + gj;
+        if (!dd_slot_open(A, sl, Fl)) continue;
+        const int32_t c = dd_slot_cell(A, sl);
         cell[k] = c;
         n_open++;
         const uint32_t cw = A.cinfo[c] & (0xFFu | CI_PIT_IN);
         if (cw & CI_PIT_IN) {                           // a drain waits until its pits are final from an earlier pass
             bool settled = true;
-            for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, c); e < A.n_pit && A.pin_dst[e] == c; e++) settled = settled && stamp[A.pin_src[e]] < pass;
+            for (PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, c); b.more(); b.e++) settled = settled && stamp[A.pin_src[b.e]] < pass;
             if (!settled) continue;
         }
         word[k] = cw; rem[k] = cw & 0xFFu; open[k] = true;
     }
-    // Rounds to the fixed point, one barrier each: a cell is ready in round r when all its regular in-neighbours became final
-    // in an EARLIER round (flag < r), so what this round writes -- flags = r, values of cells nobody may read yet -- cannot
-    // change what this round reads.  A lane remembers which in-neighbours it has seen final and asks only for the others.  A
-    // wavefront runs the evaluation as often as its busiest lane has ready cells in the round -- usually once.
-#define DU_SEL(a, k) ((k) == 0 ? a[0] : (k) == 1 ? a[1] : (k) == 2 ? a[2] : a[3])
+    // the rounds (their invariant: flowdist.h): a cell is ready when all its regular in-neighbours are final.  A lane remembers
+    // which in-neighbours it has seen final and asks only for the others; the evaluation runs on selected operands (DD_SEL).
     unsigned finished = 0;
-    for (unsigned r = 1;; r++) {                        // (at most 1024 rounds: every round but the last finishes a cell)
+    for (unsigned r = 1;; r++) {
         unsigned fresh = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -197,10 +146,10 @@ __global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int 
         while (todo) {
             const int k = __ffs((int)todo) - 1;
             todo &= todo - 1;
-            const int ix = DU_SEL(idx, k);
-            const int32_t c = DU_SEL(cell, k);
+            const int ix = DD_SEL(idx, k);
+            const int32_t c = DD_SEL(cell, k);
             const int li = ix / DD_H;
-            const double v = du_gather(A, c, DU_SEL(word, k), i0 + li, j0 + ix - li * DD_H, El[ix],
+            const double v = du_gather(A, c, DD_SEL(word, k), i0 + li, j0 + ix - li * DD_H, El[ix],
                 [&](int d, int32_t, double &p, double &du, double &zu, double &dx, double &dy) {
                     const int s = ix + NB_DI[d] * DD_H + NB_DJ[d];
                     p = Pl[s]; du = Dl[s]; zu = El[s]; dx = Xl[li + NB_DI[d]]; dy = Yl[li + NB_DI[d]];
@@ -217,20 +166,8 @@ __global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int 
             }
         if (!__syncthreads_or(fresh != 0)) break;
     }
-#undef DU_SEL
-    // results leave once, after the rounds
-    int n_done = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        if (finished & (1u << k)) { A.D[cell[k]] = val[k]; stamp[cell[k]] = pass; n_done++; }
-    if (n_open) atomicAdd(&s_open, n_open - n_done);
-    if (n_done) atomicAdd(&s_done, n_done);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        tile_open[tile] = s_open;
-        if (s_done) prog_w[tile] = pass;
-        tile_done[tile] = s_done;                       // (summed by k_dd_pass_sum)
-    }
+    dd_visit_end(A, pass, V, s_done, s_open, n_open, finished, [&](int k, const CellSlot &) { return cell[k]; },
+                 [&](int k, const CellSlot &) { return val[k]; });
 }
 
 // ---- queue
@@ -251,8 +188,8 @@ __global__ __launch_bounds__(256) void k_du_recount(DistArgs A)
                 for (int d = 0; d < 8; d++)
                     if ((cw & (1u << d)) && dd_is_open(A, c + NB_DI[d] * A.m + NB_DJ[d])) cnt++;
                 if (cw & CI_PIT_IN)
-                    for (int64_t e = dd_lower_bound(A.pin_dst, A.n_pit, c); e < A.n_pit && A.pin_dst[e] == c; e++)
-                        if (dd_is_open(A, A.pin_src[e])) cnt++;
+                    for (PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, c); b.more(); b.e++)
+                        if (dd_is_open(A, A.pin_src[b.e])) cnt++;
                 *dd_count(A, c) = cnt;
                 ready = cnt == 0;
             }
@@ -274,8 +211,8 @@ __device__ __forceinline__ void du_release(const DistArgs &A, int32_t v, uint32_
         dd_push(A, ready, u);
     }
     if (cw & CI_PIT_OUT) {
-        for (int64_t e = dd_lower_bound(A.pit_src, A.n_pit, v); e < A.n_pit && A.pit_src[e] == v; e++) {
-            const int32_t u = A.pit_dst[e];
+        for (PitBlock b = dd_pit_block(A.pit_src, A.n_pit, v); b.more(); b.e++) {
+            const int32_t u = A.pit_dst[b.e];
             if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
                 const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
                 if (slot < A.qcap) A.queue[slot] = u;
@@ -284,45 +221,29 @@ __device__ __forceinline__ void du_release(const DistArgs &A, int32_t v, uint32_
     }
 }
 
-__global__ __launch_bounds__(256) void k_du_level(DistArgs A)
-{
-    const int64_t lo = A.ctr[DD_LO], hi = A.ctr[DD_HI];
-    for (int64_t base = lo + (int64_t)blockIdx.x * blockDim.x; base < hi; base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t k = base + threadIdx.x;
-        int32_t v = 0;
-        uint32_t cw = 0;
-        if (k < hi) {
-            v = A.queue[k];
-            cw = A.cinfo[v];
-            const int i = v / A.m;
-            A.D[v] = du_gather(A, v, cw, i, v - i * A.m, A.kind != 0 ? A.elev[v] : 0.0,
-                [&](int d, int32_t u, double &p, double &du, double &zu, double &dx, double &dy) {
-                    p = A.prop[u]; du = A.D[u]; zu = A.kind != 0 ? A.elev[u] : 0.0; dx = A.dX2[i + NB_DI[d]]; dy = A.dY2[i + NB_DI[d]];
-                });
-        }
-        du_release(A, v, cw);
+// the value of an open cell whose in-neighbours are all final, from the planes (the level kernel's Finish)
+struct UpFinish {
+    __device__ __forceinline__ double operator()(const DistArgs &A, int32_t v, uint32_t cw) const
+    {
+        const int i = v / A.m;
+        return du_gather(A, v, cw, i, v - i * A.m, A.kind != 0 ? A.elev[v] : 0.0,
+            [&](int d, int32_t u, double &p, double &du, double &zu, double &dx, double &dy) {
+                p = A.prop[u]; du = A.D[u]; zu = A.kind != 0 ? A.elev[u] : 0.0; dx = A.dX2[i + NB_DI[d]]; dy = A.dY2[i + NB_DI[d]];
+            });
     }
-}
+};
 
 }  // namespace
 
 extern "C" int pydem_dist_up(pydem_tile *t, int kind, int stat, int edge_nan, double *out, double *ms, int64_t *levels, int64_t *n_unresolved)
 {
-    if (!t) { pydem_set_error("pydem_dist_up: no tile"); return -2; }
-    HIP_TRY(hipSetDevice(t->device));
+    PYDEM_TRY(dist_check_tile(t, "pydem_dist_up"));
     if (kind < 0 || kind > 2 || stat < 0 || stat > 2) { pydem_set_error("pydem_dist_up: kind %d / stat %d out of range (0..2)", kind, stat); return -2; }
-    if (!t->graph_valid || !t->cinfo || !t->prop || !t->have[PYDEM_PROPORTION] || !t->have[PYDEM_ELEV] || !t->spacing_set) {
-        pydem_set_error("pydem_dist_up: no flow graph on this tile (pydem_uca / pydem_build_graph first)");
-        return -3;
-    }
+    PYDEM_TRY(dist_check_graph(t, "pydem_dist_up"));
     DistArgs A;
     PYDEM_TRY(dist_state(t, A, kind, stat));
-    const dim3 rows = dist_row_grid(t);
-    return dist_schedule(t, "dist_up", DU_MIN_PER_VISIT, out, ms, levels, n_unresolved,
-        [&] { hipLaunchKernelGGL(k_du_init, rows, dim3(256), 0, t->stream, A, edge_nan); },
-        [&](int pass, int tiles_x, int tiles_y, int32_t *tile_state) {
-            hipLaunchKernelGGL(k_du_tiles, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, t->stream, A, (int32_t)pass, tiles_x, tiles_y, tile_state);
-        },
-        [&] { hipLaunchKernelGGL(k_du_recount, rows, dim3(256), 0, t->stream, A); },
-        [&](int grid) { hipLaunchKernelGGL(k_du_level, dim3(grid), dim3(256), 0, t->stream, A); });
+    return dist_sweep<du_release>(t, "dist_up", DU_MIN_PER_VISIT, A, UpClassify{edge_nan}, UpFinish{}, k_du_recount,
+        [&](dim3 grid, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state) {
+            hipLaunchKernelGGL(k_du_tiles, grid, dim3(256), 0, t->stream, A, pass, tiles_x, tiles_y, tile_state);
+        }, out, ms, levels, n_unresolved);
 }
