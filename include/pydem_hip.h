@@ -23,6 +23,8 @@
  *                             sweep of a path statistic) -- no reference method
  *   pydem_rev_accum           upslope dependence (watersheds) and reverse accumulation on the same flow graph (reverse sweep of a
  *                             linear or max recursion over the out-edges) -- no reference method
+ *   pydem_fwd_accum           decaying and transport-limited accumulation on the same flow graph (forward sweep of a linear
+ *                             recursion over the in-edges with a per-source multiplier and a per-cell cap) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -277,6 +279,39 @@ int pydem_rev_accum(pydem_tile *t, int op /* 0 sum, 1 max */,
                     const double *seed /* [n,m] host, or NULL = 0 everywhere (op 0 only) */,
                     const uint8_t *absorb /* [n,m] host mask, or NULL = none */, double absorb_value,
                     double *out /* [n,m] host, may be NULL */, double *ms, int64_t *levels, int64_t *n_unresolved);
+/* Forward accumulation with a per-cell rule: a load that is multiplied on its way out of every cell and capped on its way into
+ * every cell, swept from the divides to the outlets like pydem_dist_up (TauDEM's DinfDecayAccum and DinfTransLimAccum next to its
+ * AreaDinf; no reference method).  The in-edges of a cell c are those pydem_dist_up reads: the regular edges u -> c that survive
+ * the keep-filter of _mk_adjacency_matrix (pydem/dem_processing.py:1136-1137), of weight p or 1 - p of the SOURCE u, and the
+ * pit -> drain edges with theirs.  V is the result, I the inflow:
+ *     V[c] = I[c] = NaN             where the elevation of c is NaN and, with edge_nan != 0, where pydem_dist_up's edge rule makes
+ *                                   a cell NaN (the tile's border, the 8-neighbours of a NaN elevation);
+ *     I[c] = 0, tot = load[c]       where c has no in-edge;
+ *     otherwise, once every u_e is final, over the in-edges e = u_e -> c of weight w_e,
+ *       acc = 0; acc += w_e * (mult[u_e] * V[u_e])   (mult NULL: acc += w_e * V[u_e]);   I[c] = acc;   tot = load[c] + acc;
+ *     V[c] = tot                    (cap NULL),      V[c] = tot is NaN ? NaN : min(tot, cap[c])      (cap).
+ * A NaN that flows in stays NaN through the cap; every NaN is stored as the canonical NaN.  The in-edges are taken in ascending
+ * source order, a regular edge before a pit edge from the same source (the order of pydem_dist_up), by ONE lane per cell that
+ * pulls final values: no floating-point atomics, results identical from run to run and from schedule to schedule.  Cells on or
+ * downstream of a drainage cycle (pit edges can close one) never become ready: V and I are NaN there and the cells are counted in
+ * *n_unresolved; there is no re-seed loop.  The values are the tile's own: flow that enters through the border is not in them,
+ * and with edge_nan != 0 a value is finite only where no flow path into the cell can start outside the tile's data.
+ * What it is used for: the weighted accumulation over the graph's in-edges is mult NULL, cap NULL; a load that decays on its way
+ * down (decay in [0, 1]: the share of a cell's V that leaves it) is mult = decay; a supply routed under a transport capacity is
+ * load = supply, cap = capacity: V is the transport, (supply + I) - V the deposition.
+ * load: [n,m] host doubles; mult, cap: [n,m] host doubles or NULL (cap: +inf allowed, NaN refused on the host before any device
+ * work).  out: [n,m] host doubles (may be NULL); out_inflow: [n,m] host doubles or NULL -- I, bit for bit the acc that produced
+ * V, from one more pass over the rows that runs only when it is asked for.  *ms: device time of the sweep and of that pass
+ * (hipEvent pairs); *levels as for pydem_dist_up.  -2 when load is NULL or cap holds a NaN; -3 (no flow graph) when no pydem_uca /
+ * pydem_build_graph has run since the elevation, slope, direction or flats last changed.
+ * Writes no field of the tile, no timing and no state of the forward sweep or of the edge fix-up.  The result plane, the int32
+ * plane and the counter block are pydem_dist_down's, the plane of the load is pydem_rev_accum's seed (allocated by the first call
+ * that needs them, freed with the tile): a call overwrites the other calls' result ON THE DEVICE; arrays already returned are host
+ * copies.  mult, cap and the inflow are three more planes of the call's own (8 bytes per cell each), each allocated by the first
+ * call that uses it and freed with the tile. */
+int pydem_fwd_accum(pydem_tile *t, const double *load /* [n,m] host */, const double *mult /* [n,m] host, or NULL = 1 */,
+                    const double *cap /* [n,m] host, or NULL = none */, int edge_nan, double *out /* [n,m] host, may be NULL */,
+                    double *out_inflow /* [n,m] host, may be NULL */, double *ms, int64_t *levels, int64_t *n_unresolved);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

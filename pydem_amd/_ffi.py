@@ -85,6 +85,7 @@ SYMBOLS = {
                                   C.POINTER(C.c_int64)]),
     'pydem_dist_up': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_rev_accum': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'pydem_fwd_accum': (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_edge_update': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
     'pydem_uca_edge_round_inc': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
@@ -338,6 +339,26 @@ class Tile(object):
                                        mask.ctypes.data_as(_P) if mask is not None else None, float(absorb_value),
                                        out.ctypes.data_as(_P) if download else None, C.byref(ms), C.byref(levels), C.byref(left)))
         return out, ms.value, int(levels.value), int(left.value)
+
+    def fwd_accum(self, load, mult=None, cap=None, edge_nan=True, inflow=False, download=True):
+        """pydem_fwd_accum on the tile's flow graph: (float64 [n, m], inflow [n, m] or None, device ms, levels, unresolved
+        cells).  load: float64 of the tile's shape; mult, cap: the same or None.  inflow: bring the inflow plane back too.
+        download=False: the sweep alone (None instead of the arrays; the inflow pass still runs if asked for)."""
+        out = np.empty(self.shape, np.float64) if download else None
+        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        planes = []
+        for name, a in (('load', load), ('mult', mult), ('cap', cap)):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64)
+                if a.shape != self.shape:
+                    raise ValueError("%s of shape %r for a tile of shape %r" % (name, a.shape, self.shape))
+            planes.append(a)
+        # (download=False with inflow: the pass runs and its plane comes back -- the C-ABI has no other way to ask for it)
+        flow = np.empty(self.shape, np.float64) if inflow else None
+        ptr = lambda a: a.ctypes.data_as(_P) if a is not None else None
+        check(self.lib.pydem_fwd_accum(self._h, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), int(bool(edge_nan)), ptr(out), ptr(flow),
+                                       C.byref(ms), C.byref(levels), C.byref(left)))
+        return out, flow, ms.value, int(levels.value), int(left.value)
 
     def build_graph(self, opt):
         check(self.lib.pydem_build_graph(self._h, C.byref(opt)))

@@ -1,16 +1,18 @@
-// flowdist.h -- the engine of the three sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
-// pydem_dist_down), the forward one (flowdist_up.hip, pydem_dist_up) and the reverse accumulation (flowacc_rev.hip,
-// pydem_rev_accum).  A sweep supplies what differs -- which cells are final at the start (a Classify), the value of a cell whose
+// flowdist.h -- the engine of the four sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
+// pydem_dist_down), the forward one (flowdist_up.hip, pydem_dist_up), the reverse accumulation (flowacc_rev.hip,
+// pydem_rev_accum) and the forward accumulation (flowacc_fwd.hip, pydem_fwd_accum).  A sweep supplies what differs -- which cells are final at the start (a Classify), the value of a cell whose
 // neighbours are final (a Finish; in the tile passes, its round loop) and which side of the graph it waits for -- and takes
 // the rest from here, where every rule is written once:
 //
 //   the encoding of an open cell in the result plane, the argument block, the counter words, the wave-aggregated queue append;
 //   the accumulator of a path statistic with its fixed operand order, the edge cost;
 //   a cell's block of a sorted pit list (dd_pit_block), its facet neighbours in cell order (dd_facet_sorted) and its out-edges
-//   in the order every reverse sweep pulls them in (dd_for_out_edges);
+//   in the order every reverse sweep pulls them in (dd_for_out_edges), its in-edges in the order every forward sweep does
+//   (dd_for_in_edges);
 //   the frame of a tile visit: whether it runs, the staging of tile + halo under the stamp rule, the geometry of a thread's
 //   four cells, the store after the rounds and the tile's three words (dd_visit_begin, dd_stage, dd_slot, dd_visit_end);
-//   the init and the level kernel (k_flow_init, k_flow_level), the queue of a reverse sweep (dd_release, k_dd_recount);
+//   the init and the level kernel (k_flow_init, k_flow_level), the queue of a reverse sweep (dd_release, k_dd_recount) and of
+//   a forward one (du_release, k_du_recount), the cells a forward sweep starts from (UpClassify);
 //   the host's checks, uploads, state and schedule (dist_check_tile, dist_check_graph, dist_upload, dist_state, dist_schedule, dist_sweep).
 //
 // One call at a time owns the state (pydem_tile::dd_*): a call overwrites the others' device result.
@@ -155,6 +157,28 @@ __device__ __forceinline__ void dd_for_out_edges(const DistArgs &A, int32_t c, u
         if (hr && (!hp || rd <= pd)) { f(rd, rdi[ir], rdj[ir], rw[ir]); ir++; }
         else { const int pi = pd / A.m; f(pd, pi - i, pd - pi * A.m - j, A.pit_w[b.e]); b.e++; }
     }
+}
+
+// ---- a cell's in-edges
+// neighbour d (bit d of the graph word: NW N NE W E SW S SE, ascending cell order) has the cell as its FIRST facet neighbour
+// (weight p of the SOURCE) when it is a cardinal one, as its second (weight 1 - p) when it is a diagonal one
+__device__ __forceinline__ bool du_cardinal(int d) { return NB_DI[d] == 0 || NB_DJ[d] == 0; }
+
+// reg(d, u) for every regular in-edge u -> c from neighbour d and pit(k) for every entry k of the pit in-list whose destination
+// is c, in the order every forward sweep pulls them in: ascending source, a regular edge before a pit edge from the same
+// source.  cw: the graph word of c.
+template <class Reg, class Pit>
+__device__ __forceinline__ void dd_for_in_edges(const DistArgs &A, int32_t c, uint32_t cw, Reg reg, Pit pit)
+{
+    PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, c, (cw & CI_PIT_IN) != 0);
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        if (!(cw & (1u << d))) continue;
+        const int32_t u = c + NB_DI[d] * A.m + NB_DJ[d];
+        for (; b.more() && A.pin_src[b.e] < u; b.e++) pit(b.e);
+        reg(d, u);
+    }
+    for (; b.more(); b.e++) pit(b.e);
 }
 
 // ---- the frame of a tile visit
@@ -409,6 +433,77 @@ __global__ __launch_bounds__(256) void k_dd_recount(DistArgs A)
         dd_push(A, ready, c);
     }
 }
+
+// ---- the queue of a FORWARD sweep (flowdist_up.hip, flowacc_fwd.hip) and which cells it starts from: they depend on the graph
+// and the elevation alone, not on what is accumulated
+// every open cell counts its open in-neighbours (all values are from earlier launches); those with none start the queue
+__global__ __launch_bounds__(256) void k_du_recount(DistArgs A)
+{
+    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
+    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
+        const int j = j0 + (int)threadIdx.x;
+        bool ready = false;
+        int32_t c = 0;
+        if (j < A.m) {
+            c = i * A.m + j;
+            if (dd_is_open(A, c)) {
+                const uint32_t cw = A.cinfo[c];
+                int cnt = 0;
+#pragma unroll
+                for (int d = 0; d < 8; d++)
+                    if ((cw & (1u << d)) && dd_is_open(A, c + NB_DI[d] * A.m + NB_DJ[d])) cnt++;
+                if (cw & CI_PIT_IN)
+                    for (PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, c); b.more(); b.e++)
+                        if (dd_is_open(A, A.pin_src[b.e])) cnt++;
+                *dd_count(A, c) = cnt;
+                ready = cnt == 0;
+            }
+        }
+        dd_push(A, ready, c);
+    }
+}
+
+// cell v is final: every open cell one of its out-edges leads to has one open in-edge less.  `cw` = graph word of v, 0 for a
+// lane that holds no cell.  (A cell that was final from the start -- NaN by the edge rule -- holds a value, not a count.)
+__device__ __forceinline__ void du_release(const DistArgs &A, int32_t v, uint32_t cw)
+{
+    const int s = ci_section(cw);
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int32_t u = v + (q ? fe2r(s) * A.m + fe2c(s) : fe1r(s) * A.m + fe1c(s));
+        bool ready = false;
+        if ((cw & (q ? CI_OUT2 : CI_OUT1)) && dd_is_open(A, u)) ready = atomicSub(dd_count(A, u), 1) == 1;
+        dd_push(A, ready, u);
+    }
+    if (cw & CI_PIT_OUT) {
+        for (PitBlock b = dd_pit_block(A.pit_src, A.n_pit, v); b.more(); b.e++) {
+            const int32_t u = A.pit_dst[b.e];
+            if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
+                const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
+                if (slot < A.qcap) A.queue[slot] = u;
+            }
+        }
+    }
+}
+
+// NaN by the elevation and the edge rule; 0 where nothing flows in; the others are open
+struct UpClassify {
+    int edge_nan;
+    __device__ __forceinline__ bool operator()(const DistArgs &A, int32_t c, int i, int j, uint32_t cw, double &value) const
+    {
+        const double z = A.elev[c];
+        bool nanv = z != z;
+        if (edge_nan && !nanv) {
+            nanv = i == 0 || i == A.n - 1 || j == 0 || j == A.m - 1;
+            if (!nanv) {
+#pragma unroll
+                for (int d = 0; d < 8; d++) { const double zn = A.elev[c + NB_DI[d] * A.m + NB_DJ[d]]; nanv = nanv || zn != zn; }
+            }
+        }
+        value = nanv ? dd_nan() : 0.0;
+        return !nanv && (cw & (0xFFu | CI_PIT_IN));
+    }
+};
 
 // cells that never became ready (on or upstream of a drainage cycle): a plain NaN instead of the count
 __global__ void k_dd_unresolved(double *D, int64_t NN)

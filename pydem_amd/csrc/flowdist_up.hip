@@ -10,8 +10,8 @@
 // (diagonal) one; the cost is dd_cost with u as the source.  State, encoding, counters, switches, the frame of a tile visit,
 // the init and level kernels and the host's schedule are the engine's (flowdist.h): a call overwrites the other sweeps' result.
 //
-//   the init kernel (UpClassify): NaN where the elevation is NaN and, under edge_nan, on the tile's border and beside a NaN
-//   elevation; 0 where nothing flows in; the open pattern and the stamp elsewhere.
+//   the init kernel (UpClassify, flowdist.h): NaN where the elevation is NaN and, under edge_nan, on the tile's border and
+//   beside a NaN elevation; 0 where nothing flows in; the open pattern and the stamp elsewhere.
 //
 //   tile passes (k_du_tiles).  A cell has up to eight regular in-edges (the reverse sweep: two out-edges), so their weights and
 //   costs do not fit in registers next to four cells' state; what is staged instead is what they are made of, for tile + halo:
@@ -23,8 +23,8 @@
 //   in-edges (a drain: about one per pit): it is opened only when all its pits are final from an earlier pass, and its lane
 //   then reads their values and list entries from global memory in the round that finishes it.
 //
-//   the queue (k_du_recount, k_flow_level with du_release): plain Kahn.  k_du_recount writes the number of open in-neighbours
-//   into every open cell's slot and appends the cells with none; a level finishes the cells the previous one appended, then
+//   the queue (k_du_recount and du_release of flowdist.h, k_flow_level): plain Kahn.  k_du_recount writes the number of open
+//   in-neighbours into every open cell's slot and appends the cells with none; a level finishes the cells the previous one appended, then
 //   takes one off the counts of the open cells its one or two regular out-edges and its pit out-edges lead to (integer
 //   atomics), and the lane whose decrement is the last appends that cell.  A value is always written in a launch before the
 //   one that reads it.
@@ -36,8 +36,6 @@ namespace {
 // proportion, elevation, stamp) against 12 B in the reverse sweep's (value, stamp), whose switch point of 16 cells per visit
 // was measured; the queue's cost per cell is the same in both directions.  16 * 28 / 12 = 37.
 constexpr int64_t DU_MIN_PER_VISIT = 37;
-
-__device__ __forceinline__ bool du_cardinal(int d) { return NB_DI[d] == 0 || NB_DJ[d] == 0; }
 
 // The value of the open cell c = (i, j) whose in-neighbours are all final.  `reg(d, u, p, du, zu, dx, dy)` hands out what a
 // regular in-edge from neighbour d (cell u) needs: u's proportion, value, elevation and the cell size of u's row -- from the
@@ -64,25 +62,6 @@ __device__ __forceinline__ double du_gather(const DistArgs &A, int32_t c, uint32
     for (; b.more(); b.e++) pit(b.e);
     return dd_result(A.stat, S);
 }
-
-// NaN by the elevation and the edge rule; 0 where nothing flows in; the others are open
-struct UpClassify {
-    int edge_nan;
-    __device__ __forceinline__ bool operator()(const DistArgs &A, int32_t c, int i, int j, uint32_t cw, double &value) const
-    {
-        const double z = A.elev[c];
-        bool nanv = z != z;
-        if (edge_nan && !nanv) {
-            nanv = i == 0 || i == A.n - 1 || j == 0 || j == A.m - 1;
-            if (!nanv) {
-#pragma unroll
-                for (int d = 0; d < 8; d++) { const double zn = A.elev[c + NB_DI[d] * A.m + NB_DJ[d]]; nanv = nanv || zn != zn; }
-            }
-        }
-        value = nanv ? dd_nan() : 0.0;
-        return !nanv && (cw & (0xFFu | CI_PIT_IN));
-    }
-};
 
 // ---- tile passes (the frame and its rules: flowdist.h)
 __global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state)
@@ -168,57 +147,6 @@ __global__ __launch_bounds__(256) void k_du_tiles(DistArgs A, int32_t pass, int 
     }
     dd_visit_end(A, pass, V, s_done, s_open, n_open, finished, [&](int k, const CellSlot &) { return cell[k]; },
                  [&](int k, const CellSlot &) { return val[k]; });
-}
-
-// ---- queue
-// every open cell counts its open in-neighbours (all values are from earlier launches); those with none start the queue
-__global__ __launch_bounds__(256) void k_du_recount(DistArgs A)
-{
-    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
-    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
-        const int j = j0 + (int)threadIdx.x;
-        bool ready = false;
-        int32_t c = 0;
-        if (j < A.m) {
-            c = i * A.m + j;
-            if (dd_is_open(A, c)) {
-                const uint32_t cw = A.cinfo[c];
-                int cnt = 0;
-#pragma unroll
-                for (int d = 0; d < 8; d++)
-                    if ((cw & (1u << d)) && dd_is_open(A, c + NB_DI[d] * A.m + NB_DJ[d])) cnt++;
-                if (cw & CI_PIT_IN)
-                    for (PitBlock b = dd_pit_block(A.pin_dst, A.n_pit, c); b.more(); b.e++)
-                        if (dd_is_open(A, A.pin_src[b.e])) cnt++;
-                *dd_count(A, c) = cnt;
-                ready = cnt == 0;
-            }
-        }
-        dd_push(A, ready, c);
-    }
-}
-
-// cell v is final: every open cell one of its out-edges leads to has one open in-edge less.  `cw` = graph word of v, 0 for a
-// lane that holds no cell.  (A cell that was final from the start -- NaN by the edge rule -- holds a value, not a count.)
-__device__ __forceinline__ void du_release(const DistArgs &A, int32_t v, uint32_t cw)
-{
-    const int s = ci_section(cw);
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const int32_t u = v + (q ? fe2r(s) * A.m + fe2c(s) : fe1r(s) * A.m + fe1c(s));
-        bool ready = false;
-        if ((cw & (q ? CI_OUT2 : CI_OUT1)) && dd_is_open(A, u)) ready = atomicSub(dd_count(A, u), 1) == 1;
-        dd_push(A, ready, u);
-    }
-    if (cw & CI_PIT_OUT) {
-        for (PitBlock b = dd_pit_block(A.pit_src, A.n_pit, v); b.more(); b.e++) {
-            const int32_t u = A.pit_dst[b.e];
-            if (dd_is_open(A, u) && atomicSub(dd_count(A, u), 1) == 1) {
-                const int64_t slot = atomicAdd(A.ctr + DD_TAIL, 1);
-                if (slot < A.qcap) A.queue[slot] = u;
-            }
-        }
-    }
 }
 
 // the value of an open cell whose in-neighbours are all final, from the planes (the level kernel's Finish)

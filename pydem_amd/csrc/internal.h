@@ -122,9 +122,12 @@ struct pydem_tile {
     // pydem_dist_down (flowdist.hip) and pydem_dist_up (flowdist_up.hip), one call at a time: result plane (open cells keep their
     // count of open out- / in-edges in it), queue, target mask (dist_down with a mask only), counter block and its pinned mirror,
     // timing events; allocated by the first call of either.  pydem_rev_accum (flowacc_rev.hip) runs on the same state (the mask
-    // is its absorbing set) and owns one more plane, its seed, allocated by the first call that passes one
+    // is its absorbing set) and owns one more plane, its seed, allocated by the first call that passes one.  pydem_fwd_accum
+    // (flowacc_fwd.hip) runs on the same state too: its load goes to the seed plane, and its multiplier, its cap and the
+    // inflow it hands out are three more planes, each allocated by the first call that uses it
     double *dd_out = nullptr; int32_t *dd_queue = nullptr; uint8_t *dd_mask = nullptr;
     double *ra_seed = nullptr;
+    double *fa_mult = nullptr, *fa_cap = nullptr, *fa_inflow = nullptr;
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;

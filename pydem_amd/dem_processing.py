@@ -676,6 +676,87 @@ class DEMProcessor(object):
         self.rev_accum_stats = dict(sum=st_sum, max=st_max)
         return racc, dmax
 
+    decay_accum = None            # last calc_decay_accum (no counterpart in the reference)
+    decay_accum_stats = None      # {'ms', 'levels', 'n_unresolved', 'edge_nan'} of that call
+    trans_lim_accum = None        # last calc_trans_lim_accum: the transport ...
+    trans_lim_deposition = None   # ... and the deposition
+    trans_lim_stats = None        # {'ms', 'levels', 'n_unresolved', 'edge_nan'} of that call
+
+    def _plane_array(self, values, what, neutral):
+        """float64 plane of the tile's shape (scalars broadcast, masked cells `neutral`); ValueError before any device work.
+        NaN is refused here; what else the values must satisfy is the caller's to check."""
+        shape = tuple(self.shape)
+        if np.ma.isMaskedArray(values):
+            values = np.ma.filled(values.astype(np.float64), neutral)
+        try:
+            a = np.asarray(values, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number or an array of numbers" % what)
+        if a.ndim == 0:
+            a = np.full(shape, float(a))
+        if a.shape != shape:
+            raise ValueError("%s of shape %r for a tile of shape %r" % (what, a.shape, shape))
+        if np.isnan(a).any():
+            raise ValueError("%s must not be NaN (%d NaN values)" % (what, int(np.isnan(a).sum())))
+        return np.ascontiguousarray(a)
+
+    def _fwd_accum(self, what, load, mult, cap, edge_nan, inflow):
+        """One pydem_fwd_accum call on the flow graph of calc_uca (computed first if the tile has none): (array, inflow or
+        None, stats)."""
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if self._tile is None or 'uca' not in self._on_device:
+            self.run_uca()                     # the flow graph the recursion runs on (kept, with uca: nothing is thrown away)
+        self._ensure_tile()
+        logger.info("Starting %s calculation" % what)
+        edge_nan = bool(edge_nan)
+        out, flow, ms, levels, left = self._tile.fwd_accum(load, mult, cap, edge_nan, inflow)
+        if left:
+            warnings.warn("%d cells lie on or downstream of a circular drainage pattern: their %s is NaN" % (left, what))
+        return out, flow, dict(ms=ms, levels=levels, n_unresolved=left, edge_nan=edge_nan)
+
+    def calc_decay_accum(self, weights, decay=None, edge_nan=True):
+        """Accumulation of a per-cell load that decays on its way down (TauDEM's DinfDecayAccum; no reference method): every
+        cell holds its own `weights` plus, over the D-infinity in-edges of calc_uca, the flow-weighted share of decay x the
+        value of the cells that flow into it.  `weights`: a scalar or an array of the tile's shape, any finite values; masked
+        cells count as 0.  `decay`: the share of a cell's value that leaves it, a scalar or an array in [0, 1] (masked cells
+        1), or None: the plain weighted accumulation over the graph's in-edges.  The values are the tile's own: nothing enters
+        through the border.  NaN where the elevation is NaN and on or downstream of a drainage cycle.  edge_nan (TauDEM's edge
+        contamination, as in calc_dist_up): the tile's border cells and the neighbours of no-data cells are NaN, and so is
+        everything downstream of them -- a value is finite only where it is complete, because no flow path into the cell can
+        start outside the tile's data.  Runs on the flow graph of calc_uca (computed first if the tile has none).  Returns the
+        float64 array, kept as `decay_accum`; `decay_accum_stats` holds the call's device time, levels and unresolved cells."""
+        w = self._weights_array(weights)
+        k = None
+        if decay is not None:
+            k = self._plane_array(decay, 'decay', 1.0)
+            if not ((k >= 0.0) & (k <= 1.0)).all():
+                raise ValueError("decay must be in [0, 1] (%d values outside)" % int((~((k >= 0.0) & (k <= 1.0))).sum()))
+        out, _, st = self._fwd_accum('decaying accumulation', w, k, None, edge_nan, False)
+        self.decay_accum, self.decay_accum_stats = out, st
+        return out
+
+    def calc_trans_lim_accum(self, supply, capacity, edge_nan=True):
+        """Transport-limited accumulation (TauDEM's DinfTransLimAccum; no reference method): (transport, deposition).  Every cell
+        receives its own `supply` plus the flow-weighted transport of the cells that flow into it along the D-infinity in-edges
+        of calc_uca, passes on min(that, `capacity`) -- the transport -- and keeps the rest -- the deposition, (supply + inflow)
+        - transport: exactly 0 wherever the capacity does not bind, never negative.  `supply`: a scalar or an array of the
+        tile's shape, finite and >= 0 (masked cells 0); `capacity`: the same, >= 0, +inf allowed (masked cells +inf).  The
+        values are the tile's own; NaN, edge_nan and the flow graph as for calc_decay_accum.  Kept as `trans_lim_accum` and
+        `trans_lim_deposition`; `trans_lim_stats` holds the call's device time (sweep and inflow pass), levels and unresolved cells."""
+        s = self._plane_array(supply, 'supply', 0.0)
+        if not (np.isfinite(s).all() and (s >= 0.0).all()):
+            raise ValueError("supply must be finite and >= 0 (%d values are not)" % int((~(np.isfinite(s) & (s >= 0.0))).sum()))
+        cap = self._plane_array(capacity, 'capacity', np.inf)
+        if not (cap >= 0.0).all():
+            raise ValueError("capacity must be >= 0 (%d negative values)" % int((cap < 0.0).sum()))
+        transport, inflow, st = self._fwd_accum('transport-limited accumulation', s, None, cap, edge_nan, True)
+        with np.errstate(invalid='ignore'):
+            deposition = (s + inflow) - transport
+        self.trans_lim_accum, self.trans_lim_deposition, self.trans_lim_stats = transport, deposition, st
+        return transport, deposition
+
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
         before stored edge masks are uploaded (the graph stage resets them)."""
