@@ -25,6 +25,8 @@
  *                             linear or max recursion over the out-edges) -- no reference method
  *   pydem_fwd_accum           decaying and transport-limited accumulation on the same flow graph (forward sweep of a linear
  *                             recursion over the in-edges with a per-source multiplier and a per-cell cap) -- no reference method
+ *   pydem_stream_network      receivers, Strahler order, links and sub-basins on the same flow graph (a forward and a reverse
+ *                             sweep of a labelling over the tree of heaviest out-edges) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -312,6 +314,44 @@ int pydem_rev_accum(pydem_tile *t, int op /* 0 sum, 1 max */,
 int pydem_fwd_accum(pydem_tile *t, const double *load /* [n,m] host */, const double *mult /* [n,m] host, or NULL = 1 */,
                     const double *cap /* [n,m] host, or NULL = none */, int edge_nan, double *out /* [n,m] host, may be NULL */,
                     double *out_inflow /* [n,m] host, may be NULL */, double *ms, int64_t *levels, int64_t *n_unresolved);
+/* The stream network on the D-infinity flow graph: the receiver of every cell, the Strahler order and the link of every stream
+ * cell, the sub-basin of every cell (TauDEM's StreamNet / GridNet, done there on D8; no reference method).  The graph is the one
+ * pydem_dist_down reads.  The out-edges of a cell, in the order of that call, are the regular edges that survive the keep-filter
+ * of _mk_adjacency_matrix (pydem/dem_processing.py:1136-1137), of weights p and 1 - p, and the kept pit -> drain edges with
+ * theirs: ascending destination, a regular edge before a pit edge to the same cell.
+ *     recv[c]    the destination of the first out-edge of greatest weight in that order; -1 where c has no out-edge or a NaN
+ *                elevation.  It depends on the graph alone.  Every cell has at most one receiver: the receivers form a forest
+ *                (plus the cycles that pit edges can close).
+ *     S          the stream set: `streams`, a host mask [n,m] (non-zero = stream), or, when streams == NULL, uca >= uca_threshold
+ *                (finite, >= 0) on the tile's current uca (pending incremental edge rounds are flushed first; NaN is never a
+ *                stream).  Cells with a NaN elevation are never in S.
+ *     the stream inflows of c in S: the cells u in S with recv[u] == c, each counted once.
+ *     order[c]   (forward sweep, divides to outlets)  0 off S; 1 for c in S without a stream inflow; otherwise, with M the greatest
+ *                order among its stream inflows and k the number of inflows that have it, M + 1 if k >= 2, else M (Strahler).
+ *     link[c]    (the same sweep)  c in S is a link head iff its number of stream inflows is not 1; a cell with exactly one
+ *                belongs to that inflow's link.  The raw label of a link is its head cell + 1; 0 off S.
+ *     basin[c]   (reverse sweep, outlets to sources)  link[c] on S; off S basin[recv[c]]; 0 where recv[c] == -1.
+ * Readiness is that of pydem_dist_up and pydem_dist_down: a cell of the forward sweep waits for ALL its graph in-neighbours (the
+ * cells off S are final from the start), a cell of the reverse sweep for ALL its out-neighbours (the cells of S are); only the
+ * value rule looks at receivers.  ONE lane finishes a cell from final values, and every value is an integer: results identical
+ * from run to run and from schedule to schedule.  Cells of S on or downstream of a drainage cycle never become ready in the
+ * forward sweep: order and link are -1 there, and n_unresolved[0] counts them.  basin is -1 on or upstream of a cycle and
+ * wherever the link that is reached is -1; n_unresolved[1] counts the cells whose basin is -1.  There is no re-seed loop.
+ * receiver, order, link, basin: [n,m] host int32, each may be NULL.  receiver alone (all else NULL) runs only the pass over the
+ * rows and needs no stream set; basin != NULL runs the reverse sweep, and the forward one before it even if order and link are
+ * NULL.  ms[3]: device time of the receiver pass, the forward and the reverse sweep (hipEvent pairs; 0 for what did not run);
+ * levels[2], n_unresolved[2]: forward, reverse, levels as for pydem_dist_up / pydem_dist_down.  -2 for a uca_threshold that is not
+ * finite or negative when a sweep runs without a mask; -3 (no flow graph) when no pydem_uca / pydem_build_graph has run since
+ * the elevation, slope, direction or flats last changed, and for a threshold without the tile's uca.
+ * Writes no field of the tile, no timing and no state of the forward sweep of pydem_uca or of the edge fix-up.  The result plane,
+ * the int32 plane, the counter block and the byte mask are pydem_dist_down's and the plane that carries the forward result into
+ * the reverse sweep is pydem_rev_accum's seed: a call overwrites the other calls' result ON THE DEVICE; arrays already returned
+ * are host copies.  The receivers are two more planes of the call's own (int32 destination and a byte that says which edge it
+ * is -- 0..7: the neighbour direction NW N NE W E SW S SE, 8: a pit edge, 255: none; 5 bytes per cell), allocated by the first
+ * call and freed with the tile. */
+int pydem_stream_network(pydem_tile *t, const uint8_t *streams /* [n,m] host, or NULL */, double uca_threshold,
+                         int32_t *receiver, int32_t *order, int32_t *link, int32_t *basin /* [n,m] host, each may be NULL */,
+                         double *ms /* [3] */, int64_t levels[2], int64_t n_unresolved[2] /* forward, reverse */);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

@@ -86,6 +86,8 @@ SYMBOLS = {
     'pydem_dist_up': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_rev_accum': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_fwd_accum': (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'pydem_stream_network': (C.c_int, [_P, _P, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64)]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
     'pydem_uca_edge_update': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
     'pydem_uca_edge_round_inc': (C.c_int, [_P, C.POINTER(Options), _PP, _PP, _PP]),
@@ -359,6 +361,27 @@ class Tile(object):
         check(self.lib.pydem_fwd_accum(self._h, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), int(bool(edge_nan)), ptr(out), ptr(flow),
                                        C.byref(ms), C.byref(levels), C.byref(left)))
         return out, flow, ms.value, int(levels.value), int(left.value)
+
+    def stream_network(self, streams=None, uca_threshold=None, receiver=True, order=True, link=True, basin=True):
+        """pydem_stream_network on the tile's flow graph: ({'receiver', 'order', 'link', 'basin'}: int32 [n, m] or None, device ms
+        (receiver pass, forward sweep, reverse sweep), levels (forward, reverse), unresolved cells (forward, reverse)).
+        `streams`: a mask of the tile's shape, or None with `uca_threshold`; neither is needed for the receivers alone.  The
+        four flags say which planes to bring back: link and basin hold the raw labels (head cell + 1)."""
+        want = dict(receiver=receiver, order=order, link=link, basin=basin)
+        planes = {k: np.empty(self.shape, np.int32) if v else None for k, v in want.items()}
+        ms, levels, left = (C.c_double * 3)(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        mask = None
+        if streams is not None:
+            mask = np.ascontiguousarray(np.asarray(streams) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError("stream mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        elif uca_threshold is None and (order or link or basin):
+            raise ValueError("order, link and basin need a stream mask or a uca_threshold")
+        ptr = lambda a: a.ctypes.data_as(_P) if a is not None else None
+        check(self.lib.pydem_stream_network(self._h, ptr(mask), float(uca_threshold) if mask is None and uca_threshold is not None else 0.0,
+                                            ptr(planes['receiver']), ptr(planes['order']), ptr(planes['link']), ptr(planes['basin']),
+                                            ms, levels, left))
+        return planes, tuple(ms), tuple(int(v) for v in levels), tuple(int(v) for v in left)
 
     def build_graph(self, opt):
         check(self.lib.pydem_build_graph(self._h, C.byref(opt)))

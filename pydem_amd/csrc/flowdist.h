@@ -1,8 +1,9 @@
-// flowdist.h -- the engine of the four sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
+// flowdist.h -- the engine of the six sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
 // pydem_dist_down), the forward one (flowdist_up.hip, pydem_dist_up), the reverse accumulation (flowacc_rev.hip,
-// pydem_rev_accum) and the forward accumulation (flowacc_fwd.hip, pydem_fwd_accum).  A sweep supplies what differs -- which cells are final at the start (a Classify), the value of a cell whose
-// neighbours are final (a Finish; in the tile passes, its round loop) and which side of the graph it waits for -- and takes
-// the rest from here, where every rule is written once:
+// pydem_rev_accum), the forward accumulation (flowacc_fwd.hip, pydem_fwd_accum), and the forward and the reverse labelling of
+// the stream network (streamnet.hip, pydem_stream_network).  A sweep supplies what differs -- which cells are final at the
+// start (a Classify), the value of a cell whose neighbours are final (a Finish; in the tile passes, its round loop) and which
+// side of the graph it waits for -- and takes the rest from here, where every rule is written once:
 //
 //   the encoding of an open cell in the result plane, the argument block, the counter words, the wave-aggregated queue append;
 //   the accumulator of a path statistic with its fixed operand order, the edge cost;
@@ -31,8 +32,10 @@ constexpr int32_t DD_STAMP_OPEN = INT32_MAX;
 constexpr uint16_t DD_FL_OPEN = 0xFFFFu;
 // words of the call's counter block; behind it four words per tile: open cells after its last visit, for each parity of the
 // pass number the last pass of that parity in which it finished something, cells finished by its visit of the current pass
+// (DD_USER: a 64-bit word the schedule zeroes with the block and never reads, for what a call counts after its sweep --
+// streamnet.hip: the -1 of the basins)
 enum : int { DD_LO = 0, DD_HI = 1, DD_TAIL = 2, DD_LEVELS = 3, DD_NOPEN = 4 /* 64-bit: [4..5] */, DD_PASSDONE = 6 /* 64-bit: [6..7] */,
-             DD_VISITS = 8, DD_WORDS = 16 };
+             DD_VISITS = 8, DD_USER = 10 /* 64-bit: [10..11] */, DD_WORDS = 16 };
 
 struct DistArgs {
     const uint32_t *cinfo;
@@ -547,7 +550,10 @@ static int dist_upload(pydem_tile *t, T **plane, const T *src)
     return tile_plane_copy(t, *plane, const_cast<T *>(src), (size_t)t->NN * sizeof(T), false);
 }
 
-// the state the calls share (allocated by the first call of any, freed with the tile) and the argument block over it
+// the state the calls share (allocated by the first call of any, freed with the tile) and the argument block over it.  The
+// int32 plane (stamps, then the queue) means nothing between the end of a sweep and the next init, which rewrites every stamp:
+// streamnet.hip stages its int32 downloads in it there.  A sweep that wants to read a stamp of the call before has to give
+// that use a plane of its own first.
 static int dist_state(pydem_tile *t, DistArgs &A, int kind, int stat)
 {
     const int64_t ntiles = cdiv(t->m, DD_T) * cdiv(t->n, DD_T);

@@ -757,6 +757,53 @@ class DEMProcessor(object):
         self.trans_lim_accum, self.trans_lim_deposition, self.trans_lim_stats = transport, deposition, st
         return transport, deposition
 
+    flow_receiver = None          # last calc_flow_receiver (no counterpart in the reference)
+    stream_network = None         # last calc_stream_network: a streamnet.StreamNetwork
+    stream_network_stats = None   # {'ms', 'levels', 'n_unresolved', 'n_links', 'max_order'} of that call
+
+    def _stream_network(self, mask, thr, **planes):
+        """One pydem_stream_network call on the flow graph of calc_uca (computed first if the tile has none)."""
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if self._tile is None or 'uca' not in self._on_device:
+            self.run_uca()                     # the flow graph the network lies on (kept, with uca: nothing is thrown away)
+        self._ensure_tile()
+        logger.info("Starting stream network calculation")
+        return self._tile.stream_network(mask, thr, **planes)
+
+    def calc_flow_receiver(self):
+        """The receiver of every cell: the flat index (row * n_cols + col) of the cell its heaviest D-infinity out-edge leads to
+        -- the first of greatest weight in ascending destination order, a regular edge before a pit edge to the same cell --,
+        -1 where the cell has no out-edge or no data.  The receivers pick the one tree the flow graph of calc_uca (computed
+        first if the tile has none) contains.  Returns the int32 array, kept as `flow_receiver`."""
+        planes, _, _, _ = self._stream_network(None, None, receiver=True, order=False, link=False, basin=False)
+        self.flow_receiver = planes['receiver']
+        return self.flow_receiver
+
+    def calc_stream_network(self, uca_threshold=None, streams=None, basins=True):
+        """The stream network on the flow graph of calc_uca (TauDEM's StreamNet / GridNet, there on D8; no reference method).
+        The streams: the cells with uca >= `uca_threshold`, or `streams`, a boolean mask of the tile's shape (masked cells are
+        no streams) -- exactly one of the two.  Stream cells are joined along the receivers of calc_flow_receiver: `order` is
+        the Strahler order (0 off the streams), `link` the id of the reach between two junctions (a cell with other than one
+        stream inflow starts a link), `basin` the id of the link that a cell's receivers lead to (0: none; None with
+        basins=False), `links` a structured array with one row per link: id (1..K in ascending head-cell order), head, tail
+        (flat cells), order, n_cells and down, the id of the link below (0: none).  -1 in order, link and basin marks cells
+        that circular drainage left unresolved.  Returns the streamnet.StreamNetwork, kept as `stream_network`;
+        `stream_network_stats` holds the device times (receiver pass, forward sweep, reverse sweep), the levels and the
+        unresolved cells of the two sweeps, the number of links and the greatest order."""
+        from . import streamnet
+        mask, thr = self._dist_down_target(streams, uca_threshold, 'h', 'ave')
+        planes, ms, levels, left = self._stream_network(mask, thr, receiver=True, order=True, link=True, basin=bool(basins))
+        net = streamnet.compact_network(planes['receiver'], planes['order'], planes['link'], planes['basin'])
+        self.flow_receiver, self.stream_network = net.receiver, net
+        self.stream_network_stats = dict(ms=ms, levels=levels, n_unresolved=left, n_links=int(net.links.size),
+                                         max_order=int(net.order.max()) if net.order.size else 0)
+        if any(left):
+            warnings.warn("%d stream cells lie on or downstream of a circular drainage pattern (order and link are -1) and %d "
+                          "cells lead into it (basin is -1)" % left)
+        return net
+
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
         before stored edge masks are uploaded (the graph stage resets them)."""
