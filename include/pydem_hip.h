@@ -352,6 +352,44 @@ int pydem_fwd_accum(pydem_tile *t, const double *load /* [n,m] host */, const do
 int pydem_stream_network(pydem_tile *t, const uint8_t *streams /* [n,m] host, or NULL */, double uca_threshold,
                          int32_t *receiver, int32_t *order, int32_t *link, int32_t *basin /* [n,m] host, each may be NULL */,
                          double *ms /* [3] */, int64_t levels[2], int64_t n_unresolved[2] /* forward, reverse */);
+/* Accumulation along the receiver tree of the D-infinity flow graph: the single-flow-direction (D8-style) accumulation on the
+ * steepest D-infinity receiver and, cut at the link boundaries, the per-reach catchment totals of a stream network (the columns
+ * of TauDEM's StreamNet table; no reference method).  recv / code are exactly those of pydem_stream_network: the same pass over
+ * the rows, the same tie rule.
+ *     the tree in-neighbours of c: the cells u with recv[u] == c, each counted once (a source with two pit entries to c counts once).
+ *     S          the stream set, read only when cut != 0 and then taken exactly as pydem_stream_network takes its own: `streams`,
+ *                a host mask [n,m], or, when streams == NULL, uca >= uca_threshold; a NaN elevation is never in S.  cut == 0: S is empty.
+ *     the stream inflows of c: the tree in-neighbours of c that are in S.
+ *     taken      c takes the tree edge u -> c unless cut != 0, u is in S, and c is not the continuation of u's link -- c is not in
+ *                S, or c does not have exactly one stream inflow.  Edges from cells off S are always taken.
+ *     V[c]       NaN where the elevation is NaN and, with edge_nan != 0, on the tile's border cells and on the neighbours of NaN
+ *                elevations (pydem_dist_up's rule); those cells are final from the start.  load[c] where no graph edge enters c.
+ *                Every other cell is finished once EVERY graph in-neighbour is final (the readiness of pydem_dist_up, with all
+ *                in-neighbours, not only the tree's): op 0: acc = 0; acc += V[u] over the taken tree in-neighbours in ascending
+ *                source index; V = load + acc.  op 1 / 2: max(load, max V[u]) / min(load, min V[u]) over the same cells.  NaN if
+ *                any operand is NaN, stored canonical.
+ * NaN therefore spreads along taken tree edges only, and a cut stops it: with cut and edge_nan, a finite value at a link's tail says
+ * that link's own catchment lies wholly inside the tile's data, even where a link above it does not.  With cut, load = 1, op 0, the
+ * value at a link's tail is the number of cells of the link's sub-basin.  ONE lane finishes a cell from final values in that
+ * operand order: results identical from run to run and from schedule to schedule.  Cells on or downstream of a drainage cycle
+ * never become ready: NaN, counted in *n_unresolved; there is no re-seed loop.
+ * load: [n,m] host doubles.  out: [n,m] host doubles (may be NULL).  at / n_at / at_out: after the sweep one small kernel gathers
+ * the values at the flat cells at[0..n_at) into at_out (NULL / 0: no gather) -- a reach table needs K doubles, not a plane.  *ms:
+ * device time of the two passes over the rows (receivers, codes) and the sweep (hipEvent pairs); *levels as for pydem_dist_up.
+ * -2 for an op outside 0..2, a NULL load, a uca_threshold that is not finite or negative when it is read (cut without a mask) and
+ * an `at` entry outside [0, n m), all before any device work; -3 (no flow graph) when no pydem_uca / pydem_build_graph has run
+ * since the elevation, slope, direction or flats last changed, and for a threshold without the tile's uca.
+ * Writes no field of the tile, no timing and no state of the forward sweep of pydem_uca or of the edge fix-up.  The result plane,
+ * the int32 plane, the counter block and the byte mask are pydem_dist_down's, the plane of the load is pydem_rev_accum's seed, the
+ * receiver planes are pydem_stream_network's: a call overwrites the other calls' result ON THE DEVICE; arrays already returned
+ * are host copies.  One more byte plane of the call's own (receiver code + stream bit), allocated by the first call and freed
+ * with the tile. */
+int pydem_tree_accum(pydem_tile *t, int op /* 0 sum, 1 max, 2 min */, const double *load /* [n,m] host */,
+                     int cut /* 0 whole tree, 1 stop at link boundaries */,
+                     const uint8_t *streams /* [n,m] host or NULL */, double uca_threshold /* both read only when cut */,
+                     int edge_nan, double *out /* [n,m] host, may be NULL */,
+                     const int32_t *at, int64_t n_at, double *at_out /* values at the flat cells `at`; may be NULL / 0 */,
+                     double *ms, int64_t *levels, int64_t *n_unresolved);
 /* the flow graph of pydem_uca (section / proportion / adjacency / pit edges, dem_processing.py:1021-1382) for a tile whose
  * elevation, slope, aspect and flats were uploaded instead of computed -- what the reference's edge worker rebuilds from
  * its stores before every round (process_manager.py:227-240) and a resumed directory job needs once; it resets the tile's

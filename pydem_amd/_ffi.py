@@ -86,6 +86,8 @@ SYMBOLS = {
     'pydem_dist_up': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_rev_accum': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_fwd_accum': (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'pydem_tree_accum': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_double, C.c_int, _P, _P, C.c_int64, _P, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_stream_network': (C.c_int, [_P, _P, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64)]),
     'pydem_build_graph': (C.c_int, [_P, C.POINTER(Options)]),
@@ -361,6 +363,38 @@ class Tile(object):
         check(self.lib.pydem_fwd_accum(self._h, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), int(bool(edge_nan)), ptr(out), ptr(flow),
                                        C.byref(ms), C.byref(levels), C.byref(left)))
         return out, flow, ms.value, int(levels.value), int(left.value)
+
+    TREE_OPS = {'sum': 0, 'max': 1, 'min': 2}
+
+    def tree_accum(self, load, op='sum', streams=None, uca_threshold=None, edge_nan=True, at=None, download=True):
+        """pydem_tree_accum on the tile's flow graph: (float64 [n, m], values at the flat cells `at` or None, device ms, levels,
+        unresolved cells).  load: float64 of the tile's shape; op: 'sum' / 0, 'max' / 1 or 'min' / 2.  The accumulation is cut at
+        the link boundaries exactly when a stream set is given: `streams`, a mask of the tile's shape, or `uca_threshold`.
+        download=False: the sweep (and the gather) alone, None instead of the plane."""
+        ld = np.ascontiguousarray(load, np.float64)
+        if ld.shape != self.shape:
+            raise ValueError("load of shape %r for a tile of shape %r" % (ld.shape, self.shape))
+        mask = None
+        if streams is not None:
+            mask = np.ascontiguousarray(np.asarray(streams) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError("stream mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        cut = mask is not None or uca_threshold is not None
+        out = np.empty(self.shape, np.float64) if download else None
+        cells = vals = None
+        if at is not None:
+            cells = np.asarray(at)
+            if cells.size and (cells.min() < -2 ** 31 or cells.max() >= 2 ** 31):
+                raise ValueError("`at` holds cells outside the int32 range")
+            cells = np.ascontiguousarray(cells.ravel(), np.int32)
+            vals = np.empty(cells.size, np.float64)
+        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        ptr = lambda a: a.ctypes.data_as(_P) if a is not None else None
+        check(self.lib.pydem_tree_accum(self._h, int(self.TREE_OPS.get(op, op)), ptr(ld), int(cut), ptr(mask),
+                                        float(uca_threshold) if mask is None and uca_threshold is not None else 0.0,
+                                        int(bool(edge_nan)), ptr(out), ptr(cells), cells.size if cells is not None else 0, ptr(vals),
+                                        C.byref(ms), C.byref(levels), C.byref(left)))
+        return out, vals, ms.value, int(levels.value), int(left.value)
 
     def stream_network(self, streams=None, uca_threshold=None, receiver=True, order=True, link=True, basin=True):
         """pydem_stream_network on the tile's flow graph: ({'receiver', 'order', 'link', 'basin'}: int32 [n, m] or None, device ms

@@ -1,8 +1,9 @@
-// flowdist.h -- the engine of the six sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
+// flowdist.h -- the engine of the seven sweeps over the tile's D-infinity flow graph: the reverse path statistic (flowdist.hip,
 // pydem_dist_down), the forward one (flowdist_up.hip, pydem_dist_up), the reverse accumulation (flowacc_rev.hip,
-// pydem_rev_accum), the forward accumulation (flowacc_fwd.hip, pydem_fwd_accum), and the forward and the reverse labelling of
-// the stream network (streamnet.hip, pydem_stream_network).  A sweep supplies what differs -- which cells are final at the
-// start (a Classify), the value of a cell whose neighbours are final (a Finish; in the tile passes, its round loop) and which
+// pydem_rev_accum), the forward accumulation (flowacc_fwd.hip, pydem_fwd_accum), the forward and the reverse labelling of the
+// stream network (streamnet.hip, pydem_stream_network), and the accumulation along the receiver tree (flowacc_tree.hip,
+// pydem_tree_accum).  A sweep supplies what differs -- which cells are final at the start (a Classify), the value of a cell
+// whose neighbours are final (a Finish; in the tile passes, its round loop) and which
 // side of the graph it waits for -- and takes the rest from here, where every rule is written once:
 //
 //   the encoding of an open cell in the result plane, the argument block, the counter words, the wave-aggregated queue append;

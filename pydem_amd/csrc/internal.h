@@ -126,11 +126,14 @@ struct pydem_tile {
     // (flowacc_fwd.hip) runs on the same state too: its load goes to the seed plane, and its multiplier, its cap and the
     // inflow it hands out are three more planes, each allocated by the first call that uses it.  pydem_stream_network
     // (streamnet.hip) runs its two sweeps on the same state (the mask is its stream set, the seed plane carries the forward
-    // result into the reverse sweep) and owns the two receiver planes: destination cell and edge code
+    // result into the reverse sweep) and owns the two receiver planes: destination cell and edge code.  pydem_tree_accum
+    // (flowacc_tree.hip) runs on the same state, writes the same receiver planes, puts its load into the seed plane and owns
+    // one byte plane: receiver code and stream bit of every cell
     double *dd_out = nullptr; int32_t *dd_queue = nullptr; uint8_t *dd_mask = nullptr;
     double *ra_seed = nullptr;
     double *fa_mult = nullptr, *fa_cap = nullptr, *fa_inflow = nullptr;
     int32_t *sn_recv = nullptr; uint8_t *sn_code = nullptr;
+    uint8_t *ta_sc = nullptr;
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;

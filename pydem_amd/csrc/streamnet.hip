@@ -4,7 +4,8 @@
 // The D-infinity graph is a DAG with up to two regular out-edges per cell; the receivers pick the one tree it contains, and
 // the network is a labelling over that tree.  Three steps:
 //
-//   the receivers (k_sn_receiver): one pass over the rows.  Per cell the first out-edge of greatest weight in the order of
+//   the receivers (k_sn_receiver, in streamnet.h with the planes: flowacc_tree.hip runs the same pass): one pass over the
+//   rows.  Per cell the first out-edge of greatest weight in the order of
 //   dd_for_out_edges; its destination goes to an int32 plane, which edge it is to a byte plane (0..7: the neighbour direction
 //   in NB_DI / NB_DJ order, 8: a pit edge, 255: none).  They depend on the graph alone.
 //
@@ -35,7 +36,7 @@
 //       k_sn_unpack         VGPRs  12, no scratch, LDS      4 B, 8 waves per SIMD
 //       (the level kernels: k_flow_level<SnFwdFinish> 28 VGPRs, k_flow_level<SnRevFinish> 20; k_fa_tiles<false>: 98 VGPRs,
 //       21,072 B, 4 waves per SIMD)
-#include "flowdist.h"
+#include "streamnet.h"
 
 namespace {
 
@@ -49,43 +50,7 @@ namespace {
 constexpr int64_t SN_FWD_MIN_PER_VISIT = 37;
 constexpr int64_t SN_REV_MIN_PER_VISIT = 4;
 
-constexpr uint8_t SN_PIT = 8, SN_NONE = 255;
 constexpr int SN_MINUS = DD_USER;                       // the engine's free 64-bit counter word: the -1 of the basins (k_sn_unpack)
-
-struct SnPlanes { const int32_t *recv; const uint8_t *code; };
-
-// ---- the receivers
-// "the first out-edge of greatest weight in ascending destination order, a regular edge before a pit edge to the same cell" is
-// the greatest weight with ties going to the lower destination; the regular edges are offered first, so a pit edge of equal
-// weight to the same cell does not replace one
-__global__ __launch_bounds__(256) void k_sn_receiver(DistArgs A, int32_t *__restrict__ recv, uint8_t *__restrict__ code)
-{
-    for (int i = blockIdx.y; i < A.n; i += gridDim.y)
-    for (int j0 = blockIdx.x * blockDim.x; j0 < A.m; j0 += gridDim.x * blockDim.x) {
-        const int j = j0 + (int)threadIdx.x;
-        if (j >= A.m) continue;
-        const int32_t c = i * A.m + j;
-        const uint32_t cw = A.cinfo[c];
-        const double z = A.elev[c];
-        int32_t best = -1;
-        int bc = SN_NONE;
-        double bw = -INFINITY;
-        auto offer = [&](int32_t dst, int cd, double w) {
-            if (w > bw || (w == bw && dst < best)) { bw = w; best = dst; bc = cd; }
-        };
-        if (z == z) {
-            if (cw & (CI_OUT1 | CI_OUT2)) {
-                const Facet f = dd_facet_sorted(A, cw, A.prop[c]);
-                auto dir = [](int di, int dj) { const int q = (di + 1) * 3 + dj + 1; return q > 4 ? q - 1 : q; };
-                if (f.a.has) offer(c + f.a.di * A.m + f.a.dj, dir(f.a.di, f.a.dj), f.a.w);
-                if (f.b.has) offer(c + f.b.di * A.m + f.b.dj, dir(f.b.di, f.b.dj), f.b.w);
-            }
-            if (cw & CI_PIT_OUT)
-                for (PitBlock b = dd_pit_block(A.pit_src, A.n_pit, c); b.more(); b.e++) offer(A.pit_dst[b.e], SN_PIT, A.pit_w[b.e]);
-        }
-        recv[c] = best; code[c] = (uint8_t)bc;
-    }
-}
 
 // ---- order and links: the value of a stream cell, and its rule
 __device__ __forceinline__ double sn_pack(int order, int64_t head1) { return (double)((int64_t)order + 64 * head1); }
@@ -369,21 +334,9 @@ extern "C" int pydem_stream_network(pydem_tile *t, const uint8_t *streams, doubl
 {
     PYDEM_TRY(dist_check_tile(t, "pydem_stream_network"));
     const bool sweeps = order || link || basin;
-    if (sweeps && !streams && !(uca_threshold >= 0.0 && uca_threshold < INFINITY)) {
-        pydem_set_error("pydem_stream_network: uca_threshold must be finite and >= 0 when no stream mask is given (got %g)", uca_threshold);
-        return -2;
-    }
+    if (sweeps) PYDEM_TRY(sn_check_threshold("pydem_stream_network", streams, uca_threshold));
     PYDEM_TRY(dist_check_graph(t, "pydem_stream_network"));
-    if (sweeps) {
-        if (streams) PYDEM_TRY(dist_upload(t, &t->dd_mask, streams));
-        else {
-            if (!t->uca || !t->have[PYDEM_UCA]) { pydem_set_error("pydem_stream_network: uca_threshold needs the tile's uca (pydem_uca first)"); return -3; }
-            PYDEM_TRY(stage_edge_flush(t));         // incremental edge rounds: the areas the threshold reads are settled first
-        }
-    }
-    // The receivers are written again by every call, though they depend on the graph alone and the planes stay with the tile:
-    // a flag "the planes match the graph" would have to be cleared by every writer of the graph words, the proportion and the
-    // pit lists (tile.hip, uca.hip, uca_edge.hip, pits.hip), and one pass over the rows is 5 % of a call with both sweeps.
+    if (sweeps) PYDEM_TRY(sn_stream_set(t, "pydem_stream_network", streams));
     PYDEM_TRY(tile_alloc(t, &t->sn_recv, (size_t)t->NN));
     PYDEM_TRY(tile_alloc(t, &t->sn_code, (size_t)t->NN));
     DistArgs A;
@@ -393,8 +346,7 @@ extern "C" int pydem_stream_network(pydem_tile *t, const uint8_t *streams, doubl
     int64_t part_levels[2] = {0, 0}, part_left[2] = {0, 0};
     {
         HIP_TRY(hipEventRecord(t->dd_ev[0], t->stream));
-        hipLaunchKernelGGL(k_sn_receiver, dist_row_grid(t), dim3(256), 0, t->stream, A, t->sn_recv, t->sn_code);
-        HIP_TRY(hipGetLastError());
+        PYDEM_TRY(sn_receivers(t, A));               // (streamnet.h)
         HIP_TRY(hipEventRecord(t->dd_ev[1], t->stream));
         HIP_TRY(hipEventSynchronize(t->dd_ev[1]));
         float el = 0.f;

@@ -583,7 +583,7 @@ int pydem_tile_destroy(pydem_tile *t)
                     t->estamp, t->edelta, t->p_delta, t->s_data, t->p_flags, t->s_flags, t->line_stage, t->contrib,
                     t->eseed, t->lines_stage, t->pits.sort_buf, t->nd_rec, t->cond_mem, t->cb_mem[0], t->cb_mem[1], t->cb_mem[2],
                     t->dd_out, t->dd_queue, t->dd_mask, t->dd_ctr, t->ra_seed, t->fa_mult, t->fa_cap, t->fa_inflow,
-                    t->sn_recv, t->sn_code};
+                    t->sn_recv, t->sn_code, t->ta_sc};
     for (void *p : ptrs) if (p) plane_give(t->device, p);          // (blocks that did not come from tile_alloc are freed)
     if (t->h_counters) (void)hipHostFree(t->h_counters);
     if (t->h_strip_d) (void)hipHostFree(t->h_strip_d);

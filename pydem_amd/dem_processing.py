@@ -804,6 +804,99 @@ class DEMProcessor(object):
                           "cells lead into it (basin is -1)" % left)
         return net
 
+    tree_accum = None             # last calc_tree_accum (no counterpart in the reference)
+    tree_accum_stats = None       # {'ms', 'levels', 'n_unresolved', 'edge_nan', 'cut'} of that call
+    reach_attributes = None       # last calc_reach_attributes: one row per link of `stream_network`
+    reach_attributes_stats = None     # {'ms', 'sweeps': {column: {'ms', 'levels', 'n_unresolved'}}, 'edge_nan', 'n_links'}
+
+    def _tree_accum(self, load, op, mask, thr, edge_nan, at=None, download=True):
+        """One pydem_tree_accum call on the flow graph of calc_uca (computed first if the tile has none): (array or None, values
+        at `at` or None, stats)."""
+        if not self.drain_pits and (self.drain_flats or self.drain_pits_spill):
+            raise NotImplementedError("drain_flats / drain_pits_spill (without drain_pits) are not implemented on the "
+                                      "device path; use drain_pits=True (the reference default) or leave both off")
+        if self._tile is None or 'uca' not in self._on_device:
+            self.run_uca()                     # the flow graph the tree lies in (kept, with uca: nothing is thrown away)
+        self._ensure_tile()
+        logger.info("Starting receiver-tree accumulation")
+        edge_nan = bool(edge_nan)
+        out, vals, ms, levels, left = self._tile.tree_accum(load, op, mask, thr, edge_nan, at, download)
+        return out, vals, dict(ms=ms, levels=levels, n_unresolved=left, edge_nan=edge_nan, cut=mask is not None or thr is not None)
+
+    def _cell_area_plane(self):
+        return np.ascontiguousarray(np.broadcast_to((self.dX2 * self.dY2)[:, None], tuple(self.shape)))
+
+    def calc_tree_accum(self, weights=None, op='sum', streams=None, uca_threshold=None, edge_nan=True):
+        """Accumulation along the receiver tree (the single-flow-direction, D8-style accumulation on the steepest D-infinity
+        receiver of calc_flow_receiver; no reference method): every cell holds the `op` ('sum', 'max' or 'min') of its own
+        `weights` and the values of the cells whose receiver it is.  `weights`: a scalar or an array of the tile's shape, any
+        finite values (masked cells 0), or None: the cell area dX2 * dY2, which makes the sum the D8-style contributing area.
+        With a stream set -- `streams`, a boolean mask of the tile's shape, or `uca_threshold`, not both -- the accumulation is
+        cut at the link boundaries of calc_stream_network: a stream cell passes its value on only to the cell that continues its
+        link, so the value at a link's tail is the reduction over that link's own sub-basin.  NaN where the elevation is NaN
+        and on or downstream of a drainage cycle.  edge_nan (as in calc_dist_up): the tile's border cells and the neighbours of
+        no-data cells are NaN, and so is what their values reach along the tree -- a cut stops that too, so a finite value
+        under a cut says the link's own catchment lies inside the tile's data.  Runs on the flow graph of calc_uca (computed
+        first if the tile has none).  Returns the float64 array, kept as `tree_accum`; `tree_accum_stats` holds the call's
+        device time, levels, unresolved cells, edge_nan and cut."""
+        if op not in _ffi.Tile.TREE_OPS:
+            raise ValueError("op must be one of 'sum', 'max', 'min' (got %r)" % (op,))
+        if streams is not None and uca_threshold is not None:
+            raise ValueError("give at most one of streams (a mask) and uca_threshold")
+        mask = thr = None
+        if streams is not None or uca_threshold is not None:
+            mask, thr = self._dist_down_target(streams, uca_threshold, 'h', 'ave')
+        w = self._cell_area_plane() if weights is None else self._weights_array(weights)
+        out, _, st = self._tree_accum(w, op, mask, thr, edge_nan)
+        if st['n_unresolved']:
+            warnings.warn("%d cells lie on or downstream of a circular drainage pattern: their tree accumulation is NaN" % st['n_unresolved'])
+        self.tree_accum, self.tree_accum_stats = out, st
+        return out
+
+    def calc_reach_attributes(self, uca_threshold=None, streams=None, values=None, edge_nan=True):
+        """The attribute table of the stream network's reaches (TauDEM's StreamNet table; no reference method).  Runs
+        calc_stream_network(basins=False) for the stream set -- `uca_threshold` or `streams`, exactly one -- and then one
+        receiver-tree accumulation (calc_tree_accum's) per catchment column, each read at the link tails only.  Returns a
+        structured array with one row per link, in the order of `stream_network.links`:
+            id; length, the channel length along the receivers (streamnet.channel_attributes states the formulas); drop =
+            elev[head] - elev[tail]; slope = drop / length (NaN for a one-cell link); straight, the head-to-tail distance;
+            local_cells / local_area, the cells / area of the link's own sub-basin (cut at the link boundaries); total_area, the
+            area of everything whose receivers lead to the link's tail; magnitude, the Shreve magnitude (the sources above the
+            tail); complete = local_area is finite; with `values` (an array of the tile's shape, masked cells NaN, NaN allowed)
+            also v_sum, v_mean = v_sum / local_cells, v_min and v_max of it over the link's own sub-basin.
+        The catchment columns are the tile's own: with edge_nan a column is NaN where the cells it covers may continue beyond
+        the tile's data (for the cut columns: only this link's sub-basin), and on or downstream of circular drainage.  Kept as
+        `reach_attributes`; `reach_attributes_stats` holds the device time of all sweeps and the stats of each."""
+        from . import streamnet
+        mask, thr = self._dist_down_target(streams, uca_threshold, 'h', 'ave')
+        vals = None
+        if values is not None:
+            if np.ma.isMaskedArray(values):
+                values = np.ma.filled(values.astype(np.float64), np.nan)
+            try:
+                vals = np.ascontiguousarray(values, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("values must be an array of numbers")
+            if vals.shape != tuple(self.shape):
+                raise ValueError("values of shape %r for a tile of shape %r" % (vals.shape, tuple(self.shape)))
+        net = self.calc_stream_network(uca_threshold=thr, streams=mask, basins=False)
+        tails = net.links['tail']
+        area = self._cell_area_plane()
+        ones = np.ones(tuple(self.shape), np.float64)
+        sweeps = [('local_cells', ones, 'sum', True), ('local_area', area, 'sum', True), ('total_area', area, 'sum', False),
+                  ('magnitude', streamnet.magnitude_load(net), 'sum', False)]
+        if vals is not None:
+            sweeps += [('v_sum', vals, 'sum', True), ('v_min', vals, 'min', True), ('v_max', vals, 'max', True)]
+        at_tails, stats = {}, {}
+        for name, load, op, cut in sweeps:
+            _, at_tails[name], st = self._tree_accum(load, op, mask if cut else None, thr if cut else None, edge_nan, tails, False)
+            stats[name] = dict(ms=st['ms'], levels=st['levels'], n_unresolved=st['n_unresolved'])
+        table = streamnet.reach_table(net, self.elev, self.dX2, self.dY2, at_tails)
+        self.reach_attributes = table
+        self.reach_attributes_stats = dict(ms=sum(st['ms'] for st in stats.values()), sweeps=stats, edge_nan=bool(edge_nan),
+                                           n_links=int(table.size))
+        return table
+
     def build_graph(self):
         """The flow graph for a tile whose slope / aspect were set instead of computed (a resumed directory job): built now,
         before stored edge masks are uploaded (the graph stage resets them)."""
