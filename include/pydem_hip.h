@@ -27,6 +27,8 @@
  *                             recursion over the in-edges with a per-source multiplier and a per-cell cap) -- no reference method
  *   pydem_stream_network      receivers, Strahler order, links and sub-basins on the same flow graph (a forward and a reverse
  *                             sweep of a labelling over the tree of heaviest out-edges) -- no reference method
+ *   pydem_fill_depressions    depression filling of the resident elevation (PitRemove / priority-flood + epsilon: the greatest
+ *                             fixed point of a monotone recursion, by coloured LDS block relaxation) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -164,6 +166,39 @@ int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);
 int pydem_pit_candidates_read(pydem_tile *t, int64_t npits, int32_t *cells, double *elev);
 int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_iter, int max_dist, double max_dist_XY,
                     int64_t *n_failed, int64_t *iter_used, int64_t *rounds, int *needs_host);
+/* Depression filling on the resident float64 elevation z (csrc/fill_depressions.hip): TauDEM's PitRemove, Planchon & Darboux 2001,
+ * priority-flood + epsilon (Barnes et al. 2014); no reference method.  The other two conditioning stages leave every depression
+ * wider than their reach a sink; this one leaves none.  NaN is no data; a +-inf in z is refused (-2).  A cell is OPEN when
+ *     its elevation is finite and it lies on the tile's border (row 0, row n-1, column 0, column m-1), or
+ *     its elevation is finite and one of its 8 neighbours is NaN (no data is "outside", as in pydem_dist_up's edge rule), or
+ *     the caller marks it in `outlets` (uint8 [n,m] on the host, may be NULL): known sinks that must stay (TauDEM's depression mask).
+ * The filled surface W is
+ *     W[c] = NaN                                                      where z[c] is NaN,
+ *     W[c] = z[c]                                                     on open cells,
+ *     W[c] = max(z[c], min over the finite 8-neighbours v of (W[v] + eps))    on every other cell
+ * (a plain fp64 add, a plain compare that keeps z[c] unless the sum is greater, the same eps for all eight neighbours), and of the
+ * solutions of that recursion the GREATEST: what relaxing downward from +inf and a priority flood from the open cells both compute.
+ * The recursion is monotone in W, in floating point too, so the result does not depend on the order of the relaxation: it is
+ * compared bit for bit with a heap-ordered flood on the host (pydem_amd/conditioning.py: fill_depressions).  With eps == 0 this is
+ * the classic fill: lakes become flats and every value of W is a value of z.  With eps > 0 every cell that is not open has a
+ * neighbour lower by at least eps, so no interior pit or flat remains -- and flat areas that are NOT depressions get the same
+ * gradient of eps per step toward the open cells.
+ *   *epsilon (in/out): a finite value >= 0 is used as given; < 0 is automatic, 2^-32 times the smallest power of two >= max |z| over
+ *   the finite cells (1.0 if that maximum is 0); the value used is written back.  -2 for a non-finite value and for an eps > 0 with
+ *   amax + eps == amax (amax = max |z|): it would vanish at the surface's magnitude.
+ *   depth (float64 [n,m] on the host, may be NULL): W - z, exact, NaN where z is NaN.  *n_raised: cells with W > z.  *max_depth:
+ *   the largest W - z.  *passes: full passes over the grid of 32 x 32 blocks, the last one, which changed nothing, included.
+ *   *ms: device time (a hipEvent pair).
+ * The call replaces the resident elevation by W and, like the other conditioning stages, invalidates the flow graph and every
+ * field computed from the elevation (PYDEM_MAG onward).  With eps > 0 the elevation counts as float64 from then on; with eps == 0
+ * it keeps the dtype of its upload (its values are still values of that dtype).  Scratch comes from the conditioning arena:
+ * pydem_tile_device_bytes is what it was before.  -2 (bad arguments, checked before the surface is touched); -5 when
+ * PYDEM_FILL_MAX_PASSES passes (default 100000, read per call) did not reach the fixed point: W lives in scratch until the end,
+ * so the elevation is then exactly what it was.  PYDEM_FILL_LOCAL=0 (read per call): a block visit makes one relaxation step
+ * instead of iterating to its local fixed point -- the same result by another schedule, for the tests.  Per tile: a depression
+ * cut by the tile's border drains off the tile. */
+int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
+                           int64_t *passes, double *ms);
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
 /* What the tile knows about its flats mask against its slopes, and what the pydem_find_flats calls on it have launched so far

@@ -73,6 +73,8 @@ SYMBOLS = {
     'pydem_tile_synth_fractal': (C.c_int, [_P, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                            C.c_double, C.c_double]),
     'pydem_fill_flats': (C.c_int, [_P, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
+    'pydem_fill_depressions': (C.c_int, [_P, C.POINTER(C.c_double), _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'pydem_pit_candidates': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'pydem_pit_candidates_read': (C.c_int, [_P, C.c_int64, _P, _P]),
     'pydem_pit_paths': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
@@ -258,6 +260,22 @@ class Tile(object):
         check(self.lib.pydem_fill_flats(self._h, float(max_pit_area or 0.0), int(bool(below_sea)), float(source_tol), int(bool(peaks)),
                                         int(bool(pits)), int(bool(artefacts_only)), C.byref(flag)))
         return flag.value == 0
+
+    def fill_depressions(self, epsilon=None, outlets=None, want_depth=False):
+        """pydem_fill_depressions on the resident elevation: (depth or None, epsilon used, raised cells, maximum depth, passes,
+        device ms).  epsilon: None (or < 0) is automatic; outlets: a mask of the tile's shape or None."""
+        eps = C.c_double(-1.0 if epsilon is None else float(epsilon))
+        mask = None
+        if outlets is not None:
+            mask = np.ascontiguousarray(np.asarray(outlets) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError("outlets mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        depth = np.empty(self.shape, np.float64) if want_depth else None
+        raised, dmax, passes, ms = C.c_int64(0), C.c_double(0), C.c_int64(0), C.c_double(0)
+        check(self.lib.pydem_fill_depressions(self._h, C.byref(eps), mask.ctypes.data_as(_P) if mask is not None else None,
+                                              depth.ctypes.data_as(_P) if want_depth else None, C.byref(raised), C.byref(dmax),
+                                              C.byref(passes), C.byref(ms)))
+        return depth, eps.value, int(raised.value), dmax.value, int(passes.value), ms.value
 
     def pit_drain_paths(self, below_sea, max_iter, max_dist, max_dist_XY, sort_dtype=None):
         """calc_pit_drain_paths on the resident elevation.  Returns (n_failed, iterations used, rounds), or None when the tile

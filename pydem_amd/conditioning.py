@@ -127,3 +127,92 @@ def pit_drain_paths(elev, dX, dY, drain_pits_max_iter=300, drain_pits_max_dist=3
     if failed.value:
         warnings.warn("Warning %d pits had no place to drain to in this chunk" % failed.value)
     return elev, int(failed.value), int(used.value)
+
+
+# ---- depression filling (no reference method): the host twin of pydem_fill_depressions (csrc/fill_depressions.hip) ----
+def fill_depressions_epsilon(z, epsilon):
+    """The epsilon a fill of the float64 surface `z` (NaN: no data) uses, by the rules of pydem_fill_depressions
+    (include/pydem_hip.h): None is automatic, 2**-32 times the smallest power of two >= max |z| over the finite cells (1.0 if that
+    is 0); a finite value >= 0 is used as given.  ValueError for a negative or non-finite value and for one that vanishes
+    when it is added to max |z|."""
+    with np.errstate(invalid='ignore'):
+        fin = np.abs(z[np.isfinite(z)])
+    amax = float(fin.max()) if fin.size else 0.0
+    if epsilon is None:
+        if amax > 0:
+            f, e = np.frexp(amax)
+            e = int(e) - 1 if f == 0.5 else int(e)
+        else:
+            e = 0
+        with np.errstate(over='ignore', under='ignore'):
+            eps = float(np.ldexp(1.0, e - 32))
+        if not (eps > 0 and np.isfinite(eps)):
+            raise ValueError("fill_depressions: no automatic epsilon for max |z| = %r" % amax)
+    else:
+        try:
+            eps = float(epsilon)
+        except (TypeError, ValueError):
+            raise ValueError("fill_depressions: epsilon must be a number >= 0 or None (got %r)" % (epsilon,))
+        if not (np.isfinite(eps) and eps >= 0):
+            raise ValueError("fill_depressions: epsilon must be finite and >= 0, or None for the automatic value (got %r)" % (epsilon,))
+    if eps > 0 and amax + eps == amax:
+        raise ValueError("fill_depressions: epsilon %r is not representable at the surface's magnitude (max |z| = %r)" % (eps, amax))
+    return eps
+
+
+def fill_depressions(elev, epsilon=None, outlets=None):
+    """Depression filling by priority flood + epsilon (Barnes et al. 2014) with the semantics of pydem_fill_depressions
+    (include/pydem_hip.h): open cells -- the finite cells on the border, beside a no-data cell, or marked in the boolean mask
+    `outlets` -- keep their elevation, and every other finite cell becomes max(z, min over its finite 8-neighbours of (W + eps)),
+    the greatest such surface.  Masked cells and NaN are no data.  Returns (W, depth, epsilon_used): float64 arrays (depth = W - z,
+    NaN where z is) and the epsilon the call used.  It serves what the device path does not take: masked arrays, dtypes the
+    device cannot hold, tiles with fewer than three rows or columns."""
+    import heapq
+    if np.ma.isMaskedArray(elev):
+        z = np.ma.filled(elev.astype(np.float64), np.nan)
+    else:
+        z = np.array(elev, dtype=np.float64)
+    if z.ndim != 2:
+        raise ValueError("fill_depressions: a 2-D elevation array is needed (got shape %r)" % (z.shape,))
+    if np.isinf(z).any():
+        raise ValueError("fill_depressions: the elevation holds +-inf")
+    n, m = z.shape
+    nan = np.isnan(z)
+    is_open = np.zeros((n, m), bool)
+    if n and m:
+        is_open[0, :] = is_open[-1, :] = True
+        is_open[:, 0] = is_open[:, -1] = True
+    if nan.any():
+        is_open |= ndimage.binary_dilation(nan, structure=_EIGHT)
+    if outlets is not None:
+        o = np.asarray(outlets)
+        if o.shape != z.shape:
+            raise ValueError("fill_depressions: outlets of shape %r for a surface of shape %r" % (o.shape, z.shape))
+        is_open |= o.astype(bool)
+    is_open &= ~nan
+    eps = fill_depressions_epsilon(z, epsilon)
+    W = np.where(nan, np.nan, np.inf)
+    W[is_open] = z[is_open]
+    zl = z.tolist()
+    seen = (is_open | nan).tolist()
+    heap = [(zl[r][c], r, c) for r, c in zip(*np.nonzero(is_open))]
+    heapq.heapify(heap)
+    out = []
+    while heap:
+        w, r, c = heapq.heappop(heap)
+        s = w + eps                                 # (the same for the eight neighbours)
+        for rr in (r - 1, r, r + 1):
+            if rr < 0 or rr >= n:
+                continue
+            row_seen, row_z = seen[rr], zl[rr]
+            for cc in (c - 1, c, c + 1):
+                if cc < 0 or cc >= m or row_seen[cc]:
+                    continue
+                row_seen[cc] = True
+                v = s if s > row_z[cc] else row_z[cc]
+                out.append((rr, cc, v))
+                heapq.heappush(heap, (v, rr, cc))
+    if out:
+        rr, cc, vv = zip(*out)
+        W[np.array(rr), np.array(cc)] = np.array(vv, np.float64)
+    return W, W - z, eps

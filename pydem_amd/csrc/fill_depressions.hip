@@ -1,0 +1,315 @@
+// fill_depressions.hip -- pydem_fill_depressions: depression filling (PitRemove / Planchon-Darboux / priority-flood + eps) on the
+// resident elevation.  No reference method.
+//
+// The filled surface W is the GREATEST solution of
+//     W[c] = z[c]                                                  on open cells (border, beside no-data, caller's outlets)
+//     W[c] = max(z[c], min over the finite 8-neighbours v of (W[v] + eps))     elsewhere
+// (include/pydem_hip.h).  The right-hand side is monotone in W -- also in floating point: x <= y gives fl(x + eps) <= fl(y + eps)
+// -- so relaxing downward from W0 (+inf on the closed cells) in ANY order keeps every value at or above the greatest solution
+// and never raises one; what the relaxation stops at is a solution, hence that one, bit for bit.  For the same reason the
+// minimum of the eight sums is the sum of the minimum and eps: one add per cell update instead of eight.  A sum is never
+// -0.0, and max keeps z unless the sum is strictly greater, so signed zeros have one outcome too.
+//
+// Schedule: 32 x 32 blocks, one workgroup each.  A visit loads the block's W with a one-cell halo into LDS, iterates there to
+// the block's fixed point for that halo and writes the cells that fell back.  The blocks of one launch share a colour,
+// (block_row & 1) * 2 + (block_col & 1): their halos lie in blocks of the three other colours, so no workgroup of a launch
+// reads a word that another one of the same launch writes.  A block is visited only while its flag word is set: every flag is
+// set at the start, a visit clears its own, and a block whose rim cells fell sets the flags of the neighbours that read that
+// rim (plain stores of 1, read by later launches only).  A pass is the four launches; a block that changed anything stores
+// the pass number into one counter word, which the host reads through the pinned mirror every few passes.
+//
+// LDS: 34 x 34 doubles, row pitch 34 (9248 bytes).  Lane l of a wavefront reads column (l & 31) + dx of row 4 * (l >> 5) + dy:
+// the 32 lanes that ds_read_b64 serves together read 32 consecutive doubles, 256 contiguous bytes, all 64 banks once -- at
+// any pitch, so the tile is not padded.  9.2 KB and 256 threads per workgroup: the LDS admits 17 workgroups per CU, the wave
+// slots fewer: 72 VGPRs give 7 wavefronts per SIMD, so registers bound the occupancy, not LDS (profiles/fill_depressions_cost.txt).
+#include "internal.h"
+#include <math.h>
+#include <string.h>
+
+namespace {
+
+constexpr int FD_B = 32;            // block edge
+constexpr int FD_P = FD_B + 2;      // LDS tile edge and row pitch (one-cell halo)
+constexpr int FD_T = 256;           // lanes per workgroup: 32 columns x 8 groups of 4 rows
+constexpr int FD_R = FD_B * FD_B / FD_T;    // rows per lane (4)
+
+// counter block, 64-bit words
+enum { FD_AMAX = 0,     // bits of max |z| over the finite cells (non-negative doubles order like their bit patterns)
+       FD_INF = 1,      // != 0: z holds +-inf
+       FD_STAMP = 2,    // number of the last pass in which a block changed
+       FD_RAISED = 3,   // cells with W > z
+       FD_DEPTH = 4,    // bits of max (W - z)
+       FD_WORDS = 8 };
+
+__device__ inline double fd_wave_max(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(v, o); v = u > v ? u : v; }
+    return v;
+}
+
+// W0 = z on open cells, +inf on the other finite cells, NaN kept; max |z| and the +-inf test into the counter block
+__global__ void __launch_bounds__(256)
+k_fd_init(const double *__restrict__ z, const uint8_t *__restrict__ outlets, double *__restrict__ W, int n, int m,
+          unsigned long long *ctr)
+{
+    const int64_t NN = (int64_t)n * m;
+    double amax = 0.0;
+    int inf = 0;
+    for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < NN; c0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t c = c0 + threadIdx.x;
+        if (c >= NN) continue;
+        const double v = z[c];
+        if (isnan(v)) { W[c] = v; continue; }
+        if (isinf(v)) inf = 1;
+        else if (fabs(v) > amax) amax = fabs(v);
+        const int r = (int)(c / m), q = (int)(c - (int64_t)r * m);
+        bool open = r == 0 || r == n - 1 || q == 0 || q == m - 1 || (outlets && outlets[c] != 0);
+        if (!open) {
+#pragma unroll
+            for (int dr = -1; dr <= 1; dr++)
+#pragma unroll
+                for (int dq = -1; dq <= 1; dq++)
+                    if ((dr | dq) != 0 && isnan(z[c + (int64_t)dr * m + dq])) open = true;
+        }
+        W[c] = open ? v : (double)INFINITY;
+    }
+    amax = fd_wave_max(amax);
+    const unsigned long long any_inf = __ballot(inf != 0);
+    if ((threadIdx.x & 63) == 0) {
+        if (amax > 0.0) atomicMax(ctr + FD_AMAX, (unsigned long long)__double_as_longlong(amax));
+        if (any_inf) ctr[FD_INF] = 1ull;
+    }
+}
+
+// One visit of the blocks of one colour.  LOCAL: iterate in LDS to the block's fixed point for the halo it loaded; otherwise one
+// relaxation step (PYDEM_FILL_LOCAL=0: the result must not depend on the schedule).
+template <bool LOCAL>
+__global__ void __launch_bounds__(FD_T)
+k_fd_relax(const double *__restrict__ z, double *__restrict__ W, int32_t *__restrict__ flags, int n, int m, int nbr, int nbc,
+           int colour, double eps, unsigned long long stamp, unsigned long long *ctr)
+{
+    __shared__ double s[FD_P * FD_P];
+    __shared__ unsigned s_rim;
+    const int bc = 2 * (int)blockIdx.x + (colour & 1), br = 2 * (int)blockIdx.y + (colour >> 1);
+    if (br >= nbr || bc >= nbc) return;
+    const int b = br * nbc + bc;
+    if (flags[b] == 0) return;          // (nothing writes this word during the launch: the visit stores it at its end)
+    const int tid = (int)threadIdx.x, tx = tid & (FD_B - 1), ty = tid >> 5;
+    const int r0 = br * FD_B, c0 = bc * FD_B;
+    if (tid == 0) s_rim = 0u;
+    for (int i = tid; i < FD_P * FD_P; i += FD_T) {
+        const int lr = i / FD_P, lc = i - lr * FD_P;
+        const int gr = r0 - 1 + lr, gc = c0 - 1 + lc;
+        double v = (double)INFINITY;                // outside the tile and no-data: never the minimum
+        if (gr >= 0 && gr < n && gc >= 0 && gc < m) { v = W[(int64_t)gr * m + gc]; if (isnan(v)) v = (double)INFINITY; }
+        s[i] = v;
+    }
+    // the lane's cells: column tx, rows 4 ty .. 4 ty + 3 of the block; their z stays in registers (+inf where there is no
+    // cell to relax: such a cell can never fall)
+    double zz[FD_R], w0[FD_R];
+    const int gc = c0 + tx;
+#pragma unroll
+    for (int k = 0; k < FD_R; k++) {
+        const int gr = r0 + ty * FD_R + k;
+        double v = (double)INFINITY;
+        if (gr < n && gc < m) { v = z[(int64_t)gr * m + gc]; if (isnan(v)) v = (double)INFINITY; }
+        zz[k] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < FD_R; k++) w0[k] = s[(ty * FD_R + k + 1) * FD_P + tx + 1];
+    int ever = 0;
+    for (;;) {
+        double a[FD_R + 2][3];
+#pragma unroll
+        for (int j = 0; j < FD_R + 2; j++)
+#pragma unroll
+            for (int i = 0; i < 3; i++) a[j][i] = s[(ty * FD_R + j) * FD_P + tx + i];
+        bool changed = false;
+        // down the lane's four rows, then up again: a value that falls is seen by the lane's next cell at once
+#pragma unroll
+        for (int kk = 0; kk < 2 * FD_R - 1; kk++) {
+            const int k = kk < FD_R ? kk : 2 * FD_R - 2 - kk;
+            double lo = fmin(fmin(a[k][0], a[k][1]), a[k][2]);
+            lo = fmin(lo, fmin(a[k + 1][0], a[k + 1][2]));
+            lo = fmin(lo, fmin(fmin(a[k + 2][0], a[k + 2][1]), a[k + 2][2]));
+            const double sum = lo + eps;
+            const double cand = sum > zz[k] ? sum : zz[k];
+            if (cand < a[k + 1][1]) { a[k + 1][1] = cand; changed = true; }
+        }
+        __syncthreads();                            // every lane has read its window
+        if (changed) {
+#pragma unroll
+            for (int k = 0; k < FD_R; k++) s[(ty * FD_R + k + 1) * FD_P + tx + 1] = a[k + 1][1];
+        }
+        const int any = __syncthreads_or(changed ? 1 : 0);
+        ever |= any;
+        if (!LOCAL || !any) break;
+    }
+    if (!ever) {
+        if (tid == 0) flags[b] = 0;
+        return;
+    }
+    // write back what fell; which rims did
+    unsigned rim = 0u;
+#pragma unroll
+    for (int k = 0; k < FD_R; k++) {
+        const int lr = ty * FD_R + k, gr = r0 + lr;
+        const double v = s[(lr + 1) * FD_P + tx + 1];
+        if (v < w0[k]) {                            // (only cells of the tile can fall)
+            W[(int64_t)gr * m + gc] = v;
+            if (lr == 0) rim |= 1u | (tx == 0 ? 16u : 0u) | (tx == FD_B - 1 ? 32u : 0u);
+            if (lr == FD_B - 1) rim |= 2u | (tx == 0 ? 64u : 0u) | (tx == FD_B - 1 ? 128u : 0u);
+            if (tx == 0) rim |= 4u;
+            if (tx == FD_B - 1) rim |= 8u;
+        }
+    }
+    if (rim) atomicOr(&s_rim, rim);
+    __syncthreads();
+    if (tid < 8) {
+        // bit: 0 N, 1 S, 2 W, 3 E, 4 NW, 5 NE, 6 SW, 7 SE
+        const int dr = (tid == 0 || tid == 4 || tid == 5) ? -1 : ((tid == 1 || tid == 6 || tid == 7) ? 1 : 0);
+        const int dq = (tid == 2 || tid == 4 || tid == 6) ? -1 : ((tid == 3 || tid == 5 || tid == 7) ? 1 : 0);
+        const int rr = br + dr, qq = bc + dq;
+        if (((s_rim >> tid) & 1u) && rr >= 0 && rr < nbr && qq >= 0 && qq < nbc) flags[rr * nbc + qq] = 1;
+    } else if (tid == 64) {
+        flags[b] = LOCAL ? 0 : 1;                   // one step is not the fixed point: the block comes back
+        ctr[FD_STAMP] = stamp;
+    }
+}
+
+// depth = W - z (into the W plane), raised cells, maximum depth, elev = W
+__global__ void __launch_bounds__(256)
+k_fd_final(double *__restrict__ z, double *__restrict__ W, int64_t NN, unsigned long long *ctr)
+{
+    double dmax = 0.0;
+    unsigned long long cnt = 0;
+    for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < NN; c0 += (int64_t)gridDim.x * blockDim.x) {     // (uniform per wavefront)
+        const int64_t c = c0 + threadIdx.x;
+        bool up = false;
+        if (c < NN) {
+            const double w = W[c], v = z[c];
+            const double d = w - v;
+            W[c] = d;
+            up = w > v;
+            if (up) { z[c] = w; if (d > dmax) dmax = d; }
+        }
+        cnt += (unsigned long long)__popcll(__ballot(up));
+    }
+    dmax = fd_wave_max(dmax);
+    if ((threadIdx.x & 63) == 0) {
+        if (cnt) atomicAdd(ctr + FD_RAISED, cnt);
+        if (dmax > 0.0) atomicMax(ctr + FD_DEPTH, (unsigned long long)__double_as_longlong(dmax));
+    }
+}
+
+double as_double(unsigned long long b)
+{
+    double d;
+    ::memcpy(&d, &b, 8);
+    return d;
+}
+
+int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return (e && *e) ? atoi(e) : dflt;
+}
+
+}  // namespace
+
+int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised,
+                           double *max_depth, int64_t *passes, double *ms)
+{
+    const double eps_in = *epsilon;
+    if (!std::isfinite(eps_in)) { pydem_set_error("pydem_fill_depressions: epsilon must be finite (got %g)", eps_in); return -2; }
+    // read per call: the tests switch them
+    const int max_passes = env_int("PYDEM_FILL_MAX_PASSES", 100000);
+    if (max_passes < 1) { pydem_set_error("pydem_fill_depressions: PYDEM_FILL_MAX_PASSES must be >= 1"); return -2; }
+    const bool local = env_int("PYDEM_FILL_LOCAL", 1) != 0;
+    int every = env_int("PYDEM_FILL_CHECK_EVERY", 4);         // passes between two looks at the counter (the result does not depend on it)
+    if (every < 1) every = 1;
+    const int n = (int)t->n, m = (int)t->m;
+    const int nbr = (int)cdiv(n, FD_B), nbc = (int)cdiv(m, FD_B);
+    const int64_t nb = (int64_t)nbr * nbc;
+
+    ArenaLease lease;
+    PYDEM_TRY(arena_acquire(t->device, &lease));
+    double *W = (double *)arena_take(&lease, (size_t)t->NN * 8);
+    int32_t *flags = (int32_t *)arena_take(&lease, (size_t)nb * 4);
+    unsigned long long *ctr = (unsigned long long *)arena_take(&lease, FD_WORDS * 8);
+    uint8_t *d_out = outlets ? (uint8_t *)arena_take(&lease, (size_t)t->NN) : nullptr;
+    if (!W || !flags || !ctr || (outlets && !d_out)) return -1;
+    if (outlets) PYDEM_TRY(tile_plane_copy(t, d_out, const_cast<uint8_t *>(outlets), (size_t)t->NN, false));
+
+    volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;     // (64 int32: room for the block)
+    auto look = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, FD_WORDS * 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        return 0;
+    };
+    const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
+
+    HIP_TRY(hipEventRecord(t->ev[6], t->stream));
+    HIP_TRY(hipMemsetAsync(ctr, 0, FD_WORDS * 8, t->stream));
+    hipLaunchKernelGGL(k_fd_init, dim3(gcells), dim3(256), 0, t->stream, (const double *)t->elev, (const uint8_t *)d_out, W, n, m, ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)nb, t->stream));
+    PYDEM_TRY(look());
+    if (h[FD_INF]) { pydem_set_error("pydem_fill_depressions: the elevation holds +-inf"); return -2; }
+    const double amax = as_double(h[FD_AMAX]);
+    double eps = eps_in;
+    if (eps < 0) {
+        // automatic: 2^-32 of the smallest power of two >= max |z|
+        int e = 1;
+        if (amax > 0) { const double f = frexp(amax, &e); if (f == 0.5) e -= 1; } else e = 0;
+        eps = ldexp(1.0, e - 32);
+        if (!(eps > 0) || !std::isfinite(eps)) { pydem_set_error("pydem_fill_depressions: no automatic epsilon for max |z| = %g", amax); return -2; }
+    }
+    if (eps > 0 && amax + eps == amax) {
+        pydem_set_error("pydem_fill_depressions: epsilon %g is not representable at the surface's magnitude (max |z| = %g)", eps, amax);
+        return -2;
+    }
+
+    // the pass loop: bounded by max_passes
+    int64_t run = 0, stamp = 0;
+    bool converged = false;
+    while (run < max_passes) {
+        const int64_t stop = run + every < max_passes ? run + every : max_passes;
+        for (; run < stop; run++) {
+            for (int colour = 0; colour < 4; colour++) {
+                const int gx = (int)cdiv(nbc - (colour & 1), 2), gy = (int)cdiv(nbr - (colour >> 1), 2);
+                if (gx < 1 || gy < 1) continue;
+                if (local)
+                    hipLaunchKernelGGL(k_fd_relax<true>, dim3(gx, gy), dim3(FD_T), 0, t->stream, (const double *)t->elev, W, flags, n, m, nbr, nbc,
+                                       colour, eps, (unsigned long long)(run + 1), ctr);
+                else
+                    hipLaunchKernelGGL(k_fd_relax<false>, dim3(gx, gy), dim3(FD_T), 0, t->stream, (const double *)t->elev, W, flags, n, m, nbr, nbc,
+                                       colour, eps, (unsigned long long)(run + 1), ctr);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+        PYDEM_TRY(look());
+        stamp = (int64_t)h[FD_STAMP];
+        if (stamp < run) { converged = true; break; }       // the last pass enqueued changed nothing
+    }
+    if (!converged) {
+        pydem_set_error("pydem_fill_depressions: not converged after %lld passes (PYDEM_FILL_MAX_PASSES); the elevation is unchanged", (long long)run);
+        return -5;
+    }
+    hipLaunchKernelGGL(k_fd_final, dim3(gcells), dim3(256), 0, t->stream, t->elev, W, t->NN, ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, FD_WORDS * 8, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipEventRecord(t->ev[7], t->stream));
+    HIP_TRY(hipEventSynchronize(t->ev[7]));
+    float el = 0.f;
+    HIP_TRY(hipEventElapsedTime(&el, t->ev[6], t->ev[7]));
+    *epsilon = eps;
+    if (ms) *ms = (double)el;
+    if (passes) *passes = stamp + 1;            // the passes that changed something and the one that found nothing to do
+    if (n_raised) *n_raised = (int64_t)h[FD_RAISED];
+    if (max_depth) *max_depth = as_double(h[FD_DEPTH]);
+    if (eps > 0) { t->elev_f32 = false; t->elev_dtype = PYDEM_F64; }      // (eps == 0: every value of W is a value of z)
+    if (depth) PYDEM_TRY(tile_plane_copy(t, W, depth, (size_t)t->NN * 8, true));
+    return 0;
+}

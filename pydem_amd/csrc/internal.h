@@ -199,6 +199,8 @@ void tile_edge_rounds_ran(pydem_tile *t, int waves);
 void tile_watch_line(pydem_tile *t, int axis, int64_t index);
 bool tile_line_watched(const pydem_tile *t, int axis, int64_t index);
 int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double source_tol, int peaks, int pits, int artefacts_only);
+int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
+                           int64_t *passes, double *ms);
 int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);
 int stage_pit_candidates_read(pydem_tile *t, int64_t npits, int32_t *cells, double *elev);
 int stage_pit_paths(pydem_tile *t, const int32_t *order_host, int64_t npits, int max_iter, int max_dist, double max_dist_XY,

@@ -879,6 +879,23 @@ int pydem_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
     return 0;
 }
 
+int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
+                           int64_t *passes, double *ms)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_fill_depressions"));
+    if (!epsilon) { pydem_set_error("pydem_fill_depressions: epsilon is NULL"); return -2; }
+    if (t->einc_ready) PYDEM_TRY(stage_edge_flush(t));      // (pending deltas of the incremental edge rounds belong to the surface as it is)
+    // bad arguments and the pass limit leave the surface, and everything computed from it, as they were
+    PYDEM_TRY(stage_fill_depressions(t, epsilon, outlets, depth, n_raised, max_depth, passes, ms));
+    t->edge_clean = false;
+    t->einc_ready = false;
+    t->graph_valid = false;
+    t->flats_state = 0;
+    for (int f = PYDEM_MAG; f < PYDEM_FIELD_COUNT; f++) t->have[f] = false;     // as after the other conditioning stages
+    return 0;
+}
+
 int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
 {
     HIP_TRY(hipSetDevice(t->device));

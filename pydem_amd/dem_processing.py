@@ -76,6 +76,9 @@ class DEMProcessor(object):
     drain_pits_max_dist = 32
     drain_pits_max_dist_XY = None
 
+    fill_depressions = False             # run_slopes_directions fills the depressions too (calc_fill_depressions; no counterpart in the reference)
+    fill_depressions_epsilon = None      # ... with this epsilon (None: automatic)
+
     apply_uca_limit_edges = False
     apply_twi_limits = False
     apply_twi_limits_on_uca = False
@@ -107,7 +110,7 @@ class DEMProcessor(object):
                      'drain_pits_max_dist', 'drain_pits_max_dist_XY', 'apply_uca_limit_edges',
                      'apply_twi_limits', 'apply_twi_limits_on_uca', 'plotflag', 'uca_saturation_limit',
                      'twi_min_slope', 'twi_min_area', 'circular_ref_maxcount', 'maximum_pit_area',
-                     'bounds', 'transform', 'done')
+                     'bounds', 'transform', 'done', 'fill_depressions', 'fill_depressions_epsilon')
 
     elev = _Resident('elev')
     mag = _Resident('mag')
@@ -401,6 +404,72 @@ class DEMProcessor(object):
             self.elev = self.elev.astype(dtype)                # the reference edits the array in place: it keeps its dtype
         return res
 
+    fill_depth = None             # W - z of the last calc_fill_depressions(return_depth=True) (no counterpart in the reference)
+    fill_depressions_stats = None # {'epsilon', 'n_raised', 'max_depth', 'passes', 'ms'} of the last calc_fill_depressions
+
+    def calc_fill_depressions(self, epsilon=None, outlets=None, return_depth=False):
+        """Fill the depressions of the elevation (TauDEM's PitRemove, priority-flood + epsilon; no reference method), so that
+        every cell drains to the tile's border, to a no-data cell or to one of `outlets`: the filled surface W keeps the open
+        cells -- border, neighbours of no-data cells, `outlets` -- and is max(z, min over the 8 neighbours of (W + epsilon))
+        elsewhere (include/pydem_hip.h: pydem_fill_depressions).  epsilon=0 is the classic fill: lakes become flats.
+        epsilon > 0 leaves no interior pit or flat; flat areas that are not depressions get the same gradient of epsilon
+        per step toward the open cells.  epsilon=None: automatic, 2**-32 of the smallest power of two >= max |z|.
+        `outlets`: a boolean mask of the tile's shape or a sequence of (row, col) pairs: known sinks that must stay.  With
+        epsilon == 0 the array keeps its dtype (as calc_pit_drain_paths does), otherwise it becomes float64 (as after
+        calc_fill_flats).  Per tile: a depression cut by the tile's border drains off the tile.  Returns the filled
+        elevation, or (elevation, depth) with return_depth (depth = W - z, float64, kept as `fill_depth`);
+        `run_fill_depressions` is the same step without bringing the surface back to the host."""
+        self.run_fill_depressions(epsilon, outlets, return_depth)
+        return (self.elev, self.fill_depth) if return_depth else self.elev
+
+    def run_fill_depressions(self, epsilon=None, outlets=None, return_depth=False):
+        """calc_fill_depressions without the download: {'epsilon', 'n_raised', 'max_depth', 'passes', 'ms'} (epsilon as used;
+        passes and ms are 0 where the host implementation served the call), kept as `fill_depressions_stats`."""
+        if epsilon is not None:
+            try:
+                epsilon = float(epsilon)
+            except (TypeError, ValueError):
+                raise ValueError("epsilon must be a number >= 0 or None (got %r)" % (epsilon,))
+            if not (np.isfinite(epsilon) and epsilon >= 0):
+                raise ValueError("epsilon must be finite and >= 0, or None for the automatic value (got %r)" % (epsilon,))
+        mask = None if outlets is None else self._outlets_mask(outlets)
+        from . import conditioning
+        elev = self._host.get('elev')
+        dtype = None
+        on_host = False
+        if elev is not None:
+            on_host = np.ma.isMaskedArray(elev) or np.asarray(elev).dtype.kind not in 'iuf' or np.asarray(elev).ndim != 2
+            if not on_host:
+                dtype = np.asarray(elev).dtype
+                if epsilon:     # a value that vanishes at the surface's magnitude (the library would refuse it with -2)
+                    conditioning.fill_depressions_epsilon(np.asarray(elev, dtype=np.float64), epsilon)
+        if min(self.shape) < 3:
+            on_host = True
+        if on_host:
+            W, depth, eps = conditioning.fill_depressions(self.elev, epsilon, mask)
+            with np.errstate(invalid='ignore'):
+                raised = depth > 0
+            stats = dict(epsilon=eps, n_raised=int(raised.sum()), max_depth=float(depth[raised].max()) if raised.any() else 0.0,
+                         passes=0, ms=0.0)
+            if eps == 0 and dtype is not None:
+                W = W.astype(dtype)                 # (a tile too small for the device: every value is one of z)
+            self.elev = W
+        else:
+            self._ensure_tile()
+            self._push('elev')
+            logger.info("Starting depression filling")
+            depth, eps, n_raised, max_depth, passes, ms = self._tile.fill_depressions(epsilon, mask, return_depth)
+            stats = dict(epsilon=eps, n_raised=n_raised, max_depth=max_depth, passes=passes, ms=ms)
+            self._produced('elev')
+            if eps == 0 and dtype is not None and dtype != np.float64:
+                self.elev = self.elev.astype(dtype)             # every value of the classic fill is a value of the input
+        for nm in ('mag', 'direction', 'flats', 'uca', 'section', 'proportion', 'edge_todo', 'edge_done'):
+            self._on_device.discard(nm)             # the fields of the surface as it was
+            self._host.pop(nm, None)
+        self.fill_depth = depth if return_depth else None
+        self.fill_depressions_stats = stats
+        return stats
+
     def calc_slopes_directions(self, plotflag=False):
         """Slope magnitude and D-infinity direction (reference :587-619)."""
         self.run_slopes_directions()
@@ -412,6 +481,8 @@ class DEMProcessor(object):
             self.calc_fill_flats()
         if self.drain_pits_path:
             self.run_pit_drain_paths()
+        if self.fill_depressions:
+            self.run_fill_depressions(self.fill_depressions_epsilon)
         self._ensure_tile()
         self._push('elev')
         logger.info("Starting slope/direction calculation")
@@ -630,6 +701,26 @@ class DEMProcessor(object):
         self.up_dependence, self.up_dependence_stats = out, st
         return out
 
+    def _outlets_mask(self, outlets):
+        """`outlets` -- a boolean mask of the tile's shape, or a sequence of (row, col) pairs -- as a boolean mask; ValueError
+        before any device work."""
+        shape = tuple(self.shape)
+        arr = outlets if np.ma.isMaskedArray(outlets) else np.asarray(outlets)
+        pairs = arr.ndim == 2 and arr.shape[1] == 2 and arr.dtype.kind in 'iu'
+        if arr.shape == shape and (arr.dtype.kind == 'b' or not pairs):
+            return self._mask_array(arr, 'outlets')
+        if pairs or arr.size == 0:
+            arr = arr.reshape(-1, 2).astype(np.int64)
+            rows, cols = arr[:, 0], arr[:, 1]
+            bad = (rows < 0) | (rows >= shape[0]) | (cols < 0) | (cols >= shape[1])
+            if bad.any():
+                raise ValueError("outlet %r is outside the tile of shape %r" % (tuple(int(v) for v in arr[np.argmax(bad)]), shape))
+            mask = np.zeros(shape, bool)
+            mask[rows, cols] = True
+            return mask
+        raise ValueError("outlets must be a mask of shape %r or a sequence of (row, col) pairs of integers (got shape %r, dtype %s)"
+                         % (shape, arr.shape, arr.dtype))
+
     def calc_watershed(self, outlets, min_fraction=0.0):
         """The D-infinity watershed of `outlets`: the cells of which more than `min_fraction` (in [0, 1)) of the flow reaches
         an outlet -- calc_up_dependence and a comparison (NaN is outside, the outlets themselves inside).  `outlets`: a
@@ -641,22 +732,7 @@ class DEMProcessor(object):
             raise ValueError("min_fraction must be a number in [0, 1) (got %r)" % (min_fraction,))
         if not (0.0 <= frac < 1.0):
             raise ValueError("min_fraction must be in [0, 1) (got %r)" % (min_fraction,))
-        shape = tuple(self.shape)
-        arr = outlets if np.ma.isMaskedArray(outlets) else np.asarray(outlets)
-        pairs = arr.ndim == 2 and arr.shape[1] == 2 and arr.dtype.kind in 'iu'
-        if arr.shape == shape and (arr.dtype.kind == 'b' or not pairs):
-            mask = self._mask_array(arr, 'outlets')
-        elif pairs or arr.size == 0:
-            arr = arr.reshape(-1, 2).astype(np.int64)
-            rows, cols = arr[:, 0], arr[:, 1]
-            bad = (rows < 0) | (rows >= shape[0]) | (cols < 0) | (cols >= shape[1])
-            if bad.any():
-                raise ValueError("outlet %r is outside the tile of shape %r" % (tuple(int(v) for v in arr[np.argmax(bad)]), shape))
-            mask = np.zeros(shape, bool)
-            mask[rows, cols] = True
-        else:
-            raise ValueError("outlets must be a mask of shape %r or a sequence of (row, col) pairs of integers (got shape %r, dtype %s)"
-                             % (shape, arr.shape, arr.dtype))
+        mask = self._outlets_mask(outlets)
         dep = self.calc_up_dependence(mask)
         with np.errstate(invalid='ignore'):
             self.watershed = dep > frac
