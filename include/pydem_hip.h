@@ -29,6 +29,8 @@
  *                             sweep of a labelling over the tree of heaviest out-edges) -- no reference method
  *   pydem_fill_depressions    depression filling of the resident elevation (PitRemove / priority-flood + epsilon: the greatest
  *                             fixed point of a monotone recursion, by coloured LDS block relaxation) -- no reference method
+ *   pydem_depressions         the depression inventory of the resident elevation (the classic fill in scratch, a block union-find
+ *                             over the raised cells, integer per-label reductions) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -199,6 +201,56 @@ int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_
  * cut by the tile's border drains off the tile. */
 int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
                            int64_t *passes, double *ms);
+/* The depression inventory of the resident float64 elevation z (csrc/depressions.hip): which closed depressions there are, and for
+ * each where it is, how large, how deep, what volume, where it spills and where its bottom lies; no reference method.
+ * DEFINITION.  W is the classic fill of z: pydem_fill_depressions with eps = 0, the same open cells (border, beside no data, the
+ * caller's `outlets`: uint8 [n,m] on the host, may be NULL).  W lives in the conditioning arena: the call changes NEITHER the
+ * elevation NOR its dtype, the flow graph or any field computed from z, and pydem_tile_device_bytes is what it was before.  A
+ * depression is an 8-connected component of the cells with W > z.  With eps = 0 two adjacent raised cells have the same W, so a
+ * component has ONE level, its spill elevation S, and at least one sill cell: a finite cell that is not raised, is 8-adjacent to
+ * the component and has W == z == S.  Depressions are numbered 1..K in ascending order of their smallest linear cell index
+ * r*m + c.  Every value below follows from z, `outlets` and the spacing alone: the device code uses integers only (indices,
+ * counts, order-preserving bit patterns of doubles, fixed-point sums), so every schedule gives the same bits, and the host twin
+ * (pydem_amd/conditioning.py: label_depressions) is compared with array_equal.
+ * LABELS (int32 [n,m] on the host, may be NULL): the number of the kept depression a cell belongs to, 0 where no depression is
+ * kept, -1 where z is NaN.
+ * TABLE, one pydem_depression per kept depression, read with pydem_depressions_table after the call:
+ *   cells                  its cells
+ *   r0, r1, c0, c1         its bounding box (inclusive)
+ *   spill_elev             S (a copy of a value of z)
+ *   bottom, bottom_elev    the smallest linear index among its cells of lowest z (-0.0 and 0.0 are equal), and that cell's z
+ *   max_depth              spill_elev - bottom_elev, one fp64 subtraction
+ *   pour, n_sills          the smallest linear index among its sill cells, and their number (a sill cell counts once per
+ *                          depression, however many of its cells it touches)
+ *   open_sill              1 when a sill cell is an open cell: the lake spills straight off the tile, into no data or into an
+ *                          outlet, so the tile may have cut it
+ *   area, volume           sums over its cells of p = row_area[r] (= dX2[r] * dY2[r]) and of p = fl((W - z) * row_area[r]), in FIXED
+ *                          POINT: with E from frexp of the largest term possible (max row_area; fl(largest W - z of the tile * max
+ *                          row_area)), B = min(40, 62 - ceil(log2(max(n*m, 2)))) fraction bits and the quantum q = 2^(E - B), a cell
+ *                          adds llrint(p / q) (ties to even) to an int64 with an integer atomic, and the column is (double)sum * q.
+ *                          One result whatever the order, and |column - sum of p| <= cells * q / 2.  quanta[0], quanta[1]: the
+ *                          quanta of area and volume.
+ * FILTERS: a depression with max_depth < min_depth, cells < min_cells or volume < min_volume is dropped from the table and its
+ * label becomes 0; the survivors are renumbered 1..K' in the same order (0, 1, 0 keep everything).  The host decides this from the
+ * full table.  *n_found = K, *n_kept = K'.
+ * *passes: passes of the relaxation.  ms (9 doubles, may be NULL): device-clock time (hipEvent pairs) of the call and of its parts:
+ * relaxation, marking the raised cells + block-local labelling, seam merge, flatten, numbering (scan, ids), statistics, table
+ * (its download, the host's filter, the upload of the lookup: mostly host time), label write.
+ * ERRORS: -2 bad arguments (a negative or NaN filter) and +-inf in z, before any result exists; -3 without a spacing
+ * (pydem_tile_set_spacing); -5 from the fill's pass bound (PYDEM_FILL_MAX_PASSES) and for a table that contradicts the definition;
+ * -6 when the device cannot hold the table of K depressions (K can reach (n/2)(m/2)): nothing is returned, never a truncated
+ * table.  PYDEM_DEPR_LOCAL=0 (read per call): no block-local labelling, every raised cell starts as its own root and every union
+ * goes through the global merge -- the same result by another schedule, for the tests; PYDEM_FILL_LOCAL=0 does the same to the
+ * relaxation.  Per tile: a depression cut by the tile's border is open there; the nested hierarchy of depressions is not
+ * computed. */
+typedef struct pydem_depression {
+    int64_t cells, r0, r1, c0, c1, bottom, pour, n_sills, open_sill;
+    double spill_elev, bottom_elev, max_depth, area, volume;
+} pydem_depression;
+int pydem_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
+                      int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms);
+/* The table of the last pydem_depressions on this tile: `rows` must be its *n_kept (-2 otherwise). */
+int pydem_depressions_table(pydem_tile *t, int64_t rows, pydem_depression *table);
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
 /* What the tile knows about its flats mask against its slopes, and what the pydem_find_flats calls on it have launched so far

@@ -75,6 +75,9 @@ SYMBOLS = {
     'pydem_fill_flats': (C.c_int, [_P, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     'pydem_fill_depressions': (C.c_int, [_P, C.POINTER(C.c_double), _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    'pydem_depressions': (C.c_int, [_P, _P, C.c_double, C.c_int64, C.c_double, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P,
+                                    C.POINTER(C.c_int64), _P]),
+    'pydem_depressions_table': (C.c_int, [_P, C.c_int64, _P]),
     'pydem_pit_candidates': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'pydem_pit_candidates_read': (C.c_int, [_P, C.c_int64, _P, _P]),
     'pydem_pit_paths': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
@@ -276,6 +279,30 @@ class Tile(object):
                                               depth.ctypes.data_as(_P) if want_depth else None, C.byref(raised), C.byref(dmax),
                                               C.byref(passes), C.byref(ms)))
         return depth, eps.value, int(raised.value), dmax.value, int(passes.value), ms.value
+
+    # struct pydem_depression (include/pydem_hip.h)
+    DEPRESSION_ROW = np.dtype([(nm, np.int64) for nm in ('cells', 'r0', 'r1', 'c0', 'c1', 'bottom', 'pour', 'n_sills', 'open_sill')] +
+                              [(nm, np.float64) for nm in ('spill_elev', 'bottom_elev', 'max_depth', 'area', 'volume')])
+    DEPRESSION_PARTS = ('total', 'relax', 'local', 'merge', 'flatten', 'number', 'stats', 'table', 'label')
+
+    def depressions(self, outlets=None, min_depth=0.0, min_cells=1, min_volume=0.0, want_labels=True):
+        """pydem_depressions on the resident elevation: (label raster or None, rows (DEPRESSION_ROW), info) with info =
+        {'n_found', 'quanta': (area, volume), 'passes', 'ms': {part: device ms}}.  outlets: a mask of the tile's shape or None."""
+        mask = None
+        if outlets is not None:
+            mask = np.ascontiguousarray(np.asarray(outlets) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError("outlets mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        label = np.empty(self.shape, np.int32) if want_labels else None
+        found, kept, passes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        quanta, ms = np.zeros(2), np.zeros(len(self.DEPRESSION_PARTS))
+        check(self.lib.pydem_depressions(self._h, mask.ctypes.data_as(_P) if mask is not None else None, float(min_depth), int(min_cells),
+                                         float(min_volume), label.ctypes.data_as(_P) if want_labels else None, C.byref(found),
+                                         C.byref(kept), quanta.ctypes.data_as(_P), C.byref(passes), ms.ctypes.data_as(_P)))
+        rows = np.zeros(int(kept.value), self.DEPRESSION_ROW)
+        check(self.lib.pydem_depressions_table(self._h, int(kept.value), rows.ctypes.data_as(_P)))
+        return label, rows, dict(n_found=int(found.value), quanta=(float(quanta[0]), float(quanta[1])), passes=int(passes.value),
+                                 ms=dict(zip(self.DEPRESSION_PARTS, ms.tolist())))
 
     def pit_drain_paths(self, below_sea, max_iter, max_dist, max_dist_XY, sort_dtype=None):
         """calc_pit_drain_paths on the resident elevation.  Returns (n_failed, iterations used, rounds), or None when the tile

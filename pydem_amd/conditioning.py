@@ -160,22 +160,16 @@ def fill_depressions_epsilon(z, epsilon):
     return eps
 
 
-def fill_depressions(elev, epsilon=None, outlets=None):
-    """Depression filling by priority flood + epsilon (Barnes et al. 2014) with the semantics of pydem_fill_depressions
-    (include/pydem_hip.h): open cells -- the finite cells on the border, beside a no-data cell, or marked in the boolean mask
-    `outlets` -- keep their elevation, and every other finite cell becomes max(z, min over its finite 8-neighbours of (W + eps)),
-    the greatest such surface.  Masked cells and NaN are no data.  Returns (W, depth, epsilon_used): float64 arrays (depth = W - z,
-    NaN where z is) and the epsilon the call used.  It serves what the device path does not take: masked arrays, dtypes the
-    device cannot hold, tiles with fewer than three rows or columns."""
-    import heapq
+def _fill_inputs(what, elev, outlets):
+    """(z, nan, is_open) of a fill: the float64 surface (masked cells and NaN are no data), its no-data mask and its open cells"""
     if np.ma.isMaskedArray(elev):
         z = np.ma.filled(elev.astype(np.float64), np.nan)
     else:
         z = np.array(elev, dtype=np.float64)
     if z.ndim != 2:
-        raise ValueError("fill_depressions: a 2-D elevation array is needed (got shape %r)" % (z.shape,))
+        raise ValueError("%s: a 2-D elevation array is needed (got shape %r)" % (what, z.shape))
     if np.isinf(z).any():
-        raise ValueError("fill_depressions: the elevation holds +-inf")
+        raise ValueError("%s: the elevation holds +-inf" % what)
     n, m = z.shape
     nan = np.isnan(z)
     is_open = np.zeros((n, m), bool)
@@ -187,9 +181,22 @@ def fill_depressions(elev, epsilon=None, outlets=None):
     if outlets is not None:
         o = np.asarray(outlets)
         if o.shape != z.shape:
-            raise ValueError("fill_depressions: outlets of shape %r for a surface of shape %r" % (o.shape, z.shape))
+            raise ValueError("%s: outlets of shape %r for a surface of shape %r" % (what, o.shape, z.shape))
         is_open |= o.astype(bool)
     is_open &= ~nan
+    return z, nan, is_open
+
+
+def fill_depressions(elev, epsilon=None, outlets=None):
+    """Depression filling by priority flood + epsilon (Barnes et al. 2014) with the semantics of pydem_fill_depressions
+    (include/pydem_hip.h): open cells -- the finite cells on the border, beside a no-data cell, or marked in the boolean mask
+    `outlets` -- keep their elevation, and every other finite cell becomes max(z, min over its finite 8-neighbours of (W + eps)),
+    the greatest such surface.  Masked cells and NaN are no data.  Returns (W, depth, epsilon_used): float64 arrays (depth = W - z,
+    NaN where z is) and the epsilon the call used.  It serves what the device path does not take: masked arrays, dtypes the
+    device cannot hold, tiles with fewer than three rows or columns."""
+    import heapq
+    z, nan, is_open = _fill_inputs("fill_depressions", elev, outlets)
+    n, m = z.shape
     eps = fill_depressions_epsilon(z, epsilon)
     W = np.where(nan, np.nan, np.inf)
     W[is_open] = z[is_open]
@@ -216,3 +223,163 @@ def fill_depressions(elev, epsilon=None, outlets=None):
         rr, cc, vv = zip(*out)
         W[np.array(rr), np.array(cc)] = np.array(vv, np.float64)
     return W, W - z, eps
+
+
+# ---- depression inventory (no reference method): the host twin of pydem_depressions (csrc/depressions.hip) ----
+DEPRESSION_DTYPE = np.dtype([('cells', np.int64), ('r0', np.int64), ('r1', np.int64), ('c0', np.int64), ('c1', np.int64),
+                             ('spill_elev', np.float64), ('bottom_row', np.int64), ('bottom_col', np.int64), ('bottom_elev', np.float64),
+                             ('max_depth', np.float64), ('pour_row', np.int64), ('pour_col', np.int64), ('n_sills', np.int64),
+                             ('open_sill', np.int64), ('area', np.float64), ('volume', np.float64), ('mean_depth', np.float64)])
+
+
+def fixed_point(cells, largest):
+    """(shift, quantum) of the fixed-point sums of pydem_depressions: B = min(40, 62 - ceil(log2(max(cells, 2)))) fraction bits,
+    E from frexp of the largest term; a term p adds rint(ldexp(p, shift)), shift = B - E, and the quantum is 2**(E - B)."""
+    B = min(40, 62 - (max(int(cells), 2) - 1).bit_length())
+    E = int(np.frexp(float(largest))[1])
+    return B - E, float(np.ldexp(1.0, E - B))
+
+
+def depression_limits(what, **limits):
+    """the limits of a depression filter as numbers >= 0 (None stays None); ValueError otherwise"""
+    out = {}
+    for nm, v in limits.items():
+        if v is not None:
+            try:
+                v = float(v) if 'cells' not in nm else int(v)
+            except (TypeError, ValueError):
+                raise ValueError("%s: %s must be a number >= 0 (got %r)" % (what, nm, v))
+            if not (v >= 0) or not np.isfinite(v):
+                raise ValueError("%s: %s must be finite and >= 0 (got %r)" % (what, nm, v))
+        out[nm] = v
+    return out
+
+
+def depression_table(cells, r0, r1, c0, c1, spill, bottom, bottom_elev, pour, n_sills, open_sill, area, volume, m):
+    """the structured table of calc_depressions from its columns (bottom and pour as linear indices r * m + c)"""
+    t = np.zeros(len(cells), DEPRESSION_DTYPE)
+    t['cells'], t['r0'], t['r1'], t['c0'], t['c1'] = cells, r0, r1, c0, c1
+    t['spill_elev'], t['bottom_elev'] = spill, bottom_elev
+    t['bottom_row'], t['bottom_col'] = np.asarray(bottom) // m, np.asarray(bottom) % m
+    t['pour_row'], t['pour_col'] = np.asarray(pour) // m, np.asarray(pour) % m
+    t['max_depth'] = t['spill_elev'] - t['bottom_elev']
+    t['n_sills'], t['open_sill'], t['area'], t['volume'] = n_sills, open_sill, area, volume
+    t['mean_depth'] = t['volume'] / t['area']
+    return t
+
+
+def label_depressions(elev, outlets=None, min_depth=0.0, min_cells=1, min_volume=0.0, dX2dY2=None):
+    """The depression inventory with the semantics of pydem_depressions (include/pydem_hip.h): W is the classic fill (epsilon 0) of
+    the surface, a depression an 8-connected component of W > z, numbered in ascending order of its smallest linear index.  Returns
+    (label, table, quanta): the int32 label raster (0: in no kept depression, -1: no data), the structured table (DEPRESSION_DTYPE;
+    area and volume are the fixed-point sums of the header, in the units of dX2dY2 -- the cell area per row, 1 by default) and the
+    quanta (area, volume) of those sums.  Depressions below min_depth, min_cells or min_volume are dropped and the rest renumbered
+    in the same order.  It serves what the device path does not take: masked arrays, dtypes the device cannot hold, tiles with
+    fewer than three rows or columns."""
+    lim = depression_limits("label_depressions", min_depth=min_depth, min_cells=min_cells, min_volume=min_volume)
+    z, nan, is_open = _fill_inputs("label_depressions", elev, outlets)
+    n, m = z.shape
+    ra = np.ones(n) if dX2dY2 is None else np.ascontiguousarray(dX2dY2, np.float64)
+    if ra.shape != (n,):
+        raise ValueError("label_depressions: dX2dY2 of shape %r for %d rows" % (ra.shape, n))
+    W = fill_depressions(z, 0.0, outlets)[0]
+    with np.errstate(invalid='ignore'):
+        raised = W > z
+    lab, K = ndimage.label(raised, structure=_EIGHT)            # numbered in raster order of each component's first cell
+    amax = float(ra.max()) if n else 0.0
+    idx = np.flatnonzero(raised)
+    depth = W.ravel()[idx] - z.ravel()[idx]
+    sh_a, q_a = fixed_point(n * m, amax)
+    sh_v, q_v = fixed_point(n * m, (float(depth.max()) if K else 0.0) * amax)
+    label = np.where(nan, -1, 0).astype(np.int32)
+    if K == 0:
+        return label, np.zeros(0, DEPRESSION_DTYPE), (q_a, q_v)
+    order = np.argsort(lab.ravel()[idx], kind='stable')         # by label, ascending index within a label
+    idx, depth = idx[order], depth[order]
+    cells = np.bincount(lab.ravel()[idx] - 1, minlength=K).astype(np.int64)
+    first = np.concatenate(([0], np.cumsum(cells)[:-1]))
+    r, c = idx // m, idx % m
+    zc = z.ravel()[idx]
+    zmin = np.minimum.reduceat(zc, first)
+    bottom = np.minimum.reduceat(np.where(zc == np.repeat(zmin, cells), idx, n * m), first)
+    spill = W.ravel()[idx[first]]
+    area = np.add.reduceat(np.rint(np.ldexp(ra[r], sh_a)).astype(np.int64), first)
+    volume = np.add.reduceat(np.rint(np.ldexp(depth * ra[r], sh_v)).astype(np.int64), first)
+    # sills: finite cells that are not raised, beside a depression whose level is their elevation
+    cand = ~raised & ~nan
+    lp = np.pad(lab, 1)
+    Wp = np.pad(W, 1, constant_values=np.nan)
+    pairs = []
+    for dr in (0, 1, 2):
+        for dc in (0, 1, 2):
+            if dr == 1 and dc == 1:
+                continue
+            nl = lp[dr:dr + n, dc:dc + m]
+            with np.errstate(invalid='ignore'):
+                hit = cand & (nl > 0) & (Wp[dr:dr + n, dc:dc + m] == z)
+            cell = np.flatnonzero(hit)
+            pairs.append((nl.ravel()[cell].astype(np.int64) - 1) * (n * m) + cell)
+    pairs = np.unique(np.concatenate(pairs))
+    sl, sc = pairs // (n * m), pairs % (n * m)
+    n_sills = np.bincount(sl, minlength=K).astype(np.int64)
+    if (n_sills == 0).any():
+        raise RuntimeError("label_depressions: a depression without a sill cell")
+    sfirst = np.concatenate(([0], np.cumsum(n_sills)[:-1]))
+    pour = sc[sfirst]                                           # (np.unique sorted them: the smallest cell of each label comes first)
+    open_sill = np.maximum.reduceat(is_open.ravel()[sc].astype(np.int64), sfirst)
+    table = depression_table(cells, np.minimum.reduceat(r, first), np.maximum.reduceat(r, first), np.minimum.reduceat(c, first),
+                             np.maximum.reduceat(c, first), spill, bottom, z.ravel()[bottom], pour, n_sills, open_sill,
+                             area.astype(np.float64) * q_a, volume.astype(np.float64) * q_v, m)
+    keep = (table['max_depth'] >= lim['min_depth']) & (table['cells'] >= lim['min_cells']) & (table['volume'] >= lim['min_volume'])
+    lut = np.zeros(K + 1, np.int32)
+    lut[1:][keep] = np.arange(1, int(keep.sum()) + 1)
+    label = np.where(nan, -1, lut[lab]).astype(np.int32)
+    return label, table[keep], (q_a, q_v)
+
+
+def over_limits(table, max_depth=None, max_cells=None, max_volume=None):
+    """the depressions of `table` that exceed one of the given limits (boolean array)"""
+    over = np.zeros(len(table), bool)
+    if max_depth is not None:
+        over |= table['max_depth'] > max_depth
+    if max_cells is not None:
+        over |= table['cells'] > max_cells
+    if max_volume is not None:
+        over |= table['volume'] > max_volume
+    return over
+
+
+def limited_outlets(inventory, shape, outlets, max_depth, max_cells, max_volume, max_rounds):
+    """The loop of the limited fill: `inventory(mask)` returns the depression table under the outlets `mask`; the bottoms of the
+    depressions over a limit become outlets until none is over one.  Every round adds at least one new outlet (a bottom is a
+    raised cell, so it was none).  Returns (mask, kept_sinks [N, 2]); RuntimeError when max_rounds rounds did not suffice."""
+    mask = np.zeros(shape, bool) if outlets is None else np.array(outlets, dtype=bool)
+    kept = np.zeros((0, 2), np.int64)
+    for rnd in range(int(max_rounds) + 1):
+        table = inventory(mask)
+        over = over_limits(table, max_depth, max_cells, max_volume)
+        if not over.any():
+            return mask, kept
+        if rnd == int(max_rounds):
+            break
+        new = np.stack([table['bottom_row'][over], table['bottom_col'][over]], axis=1)
+        mask[new[:, 0], new[:, 1]] = True
+        kept = np.concatenate([kept, new])
+    raise RuntimeError("fill_depressions_limited: depressions over the limits remain after %d rounds (max_rounds)" % int(max_rounds))
+
+
+def fill_depressions_limited(elev, max_depth=None, max_cells=None, max_volume=None, epsilon=None, outlets=None, max_rounds=64,
+                             dX2dY2=None):
+    """The z-limit fill (ArcGIS Fill's z-limit, WhiteboxTools' max_depth): a depression deeper than max_depth, larger than
+    max_cells or holding more than max_volume is kept, everything else is filled -- the shallow depressions nested inside a kept
+    one included.  The inventory (label_depressions) is taken with the outlets collected so far, the bottoms of the depressions
+    over a limit join the outlets, and when none is over a limit one fill_depressions(epsilon, outlets=collected) follows.
+    Returns (W, depth, epsilon_used, kept_sinks): kept_sinks is the (N, 2) int array of the outlets the loop added.  RuntimeError
+    after max_rounds rounds, with the input untouched.  With no limit it is fill_depressions."""
+    lim = depression_limits("fill_depressions_limited", max_depth=max_depth, max_cells=max_cells, max_volume=max_volume)
+    z, nan, _ = _fill_inputs("fill_depressions_limited", elev, outlets)
+    if all(v is None for v in lim.values()):
+        return fill_depressions(elev, epsilon, outlets) + (np.zeros((0, 2), np.int64),)
+    mask, kept = limited_outlets(lambda o: label_depressions(z, o, dX2dY2=dX2dY2)[1], z.shape, outlets, lim['max_depth'],
+                                 lim['max_cells'], lim['max_volume'], max_rounds)
+    return fill_depressions(z, epsilon, mask) + (kept,)

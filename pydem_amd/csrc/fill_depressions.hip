@@ -218,14 +218,16 @@ int env_int(const char *name, int dflt)
 
 }  // namespace
 
-int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised,
-                           double *max_depth, int64_t *passes, double *ms)
+// The first part of the fill, shared with pydem_depressions (depressions.hip): W relaxed to its fixed point in scratch of the
+// caller's lease; the elevation is not touched.  `who` names the entry point in the messages; ev_start (may be null) is recorded
+// where the device work begins.
+int fill_relax(pydem_tile *t, ArenaLease *lease, const char *who, double *epsilon, const uint8_t *outlets, hipEvent_t ev_start, FillRelax *out)
 {
     const double eps_in = *epsilon;
-    if (!std::isfinite(eps_in)) { pydem_set_error("pydem_fill_depressions: epsilon must be finite (got %g)", eps_in); return -2; }
+    if (!std::isfinite(eps_in)) { pydem_set_error("%s: epsilon must be finite (got %g)", who, eps_in); return -2; }
     // read per call: the tests switch them
     const int max_passes = env_int("PYDEM_FILL_MAX_PASSES", 100000);
-    if (max_passes < 1) { pydem_set_error("pydem_fill_depressions: PYDEM_FILL_MAX_PASSES must be >= 1"); return -2; }
+    if (max_passes < 1) { pydem_set_error("%s: PYDEM_FILL_MAX_PASSES must be >= 1", who); return -2; }
     const bool local = env_int("PYDEM_FILL_LOCAL", 1) != 0;
     int every = env_int("PYDEM_FILL_CHECK_EVERY", 4);         // passes between two looks at the counter (the result does not depend on it)
     if (every < 1) every = 1;
@@ -233,12 +235,10 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     const int nbr = (int)cdiv(n, FD_B), nbc = (int)cdiv(m, FD_B);
     const int64_t nb = (int64_t)nbr * nbc;
 
-    ArenaLease lease;
-    PYDEM_TRY(arena_acquire(t->device, &lease));
-    double *W = (double *)arena_take(&lease, (size_t)t->NN * 8);
-    int32_t *flags = (int32_t *)arena_take(&lease, (size_t)nb * 4);
-    unsigned long long *ctr = (unsigned long long *)arena_take(&lease, FD_WORDS * 8);
-    uint8_t *d_out = outlets ? (uint8_t *)arena_take(&lease, (size_t)t->NN) : nullptr;
+    double *W = (double *)arena_take(lease, (size_t)t->NN * 8);
+    int32_t *flags = (int32_t *)arena_take(lease, (size_t)nb * 4);
+    unsigned long long *ctr = (unsigned long long *)arena_take(lease, FD_WORDS * 8);
+    uint8_t *d_out = outlets ? (uint8_t *)arena_take(lease, (size_t)t->NN) : nullptr;
     if (!W || !flags || !ctr || (outlets && !d_out)) return -1;
     if (outlets) PYDEM_TRY(tile_plane_copy(t, d_out, const_cast<uint8_t *>(outlets), (size_t)t->NN, false));
 
@@ -250,13 +250,13 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     };
     const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
 
-    HIP_TRY(hipEventRecord(t->ev[6], t->stream));
+    if (ev_start) HIP_TRY(hipEventRecord(ev_start, t->stream));
     HIP_TRY(hipMemsetAsync(ctr, 0, FD_WORDS * 8, t->stream));
     hipLaunchKernelGGL(k_fd_init, dim3(gcells), dim3(256), 0, t->stream, (const double *)t->elev, (const uint8_t *)d_out, W, n, m, ctr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)nb, t->stream));
     PYDEM_TRY(look());
-    if (h[FD_INF]) { pydem_set_error("pydem_fill_depressions: the elevation holds +-inf"); return -2; }
+    if (h[FD_INF]) { pydem_set_error("%s: the elevation holds +-inf", who); return -2; }
     const double amax = as_double(h[FD_AMAX]);
     double eps = eps_in;
     if (eps < 0) {
@@ -264,10 +264,10 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
         int e = 1;
         if (amax > 0) { const double f = frexp(amax, &e); if (f == 0.5) e -= 1; } else e = 0;
         eps = ldexp(1.0, e - 32);
-        if (!(eps > 0) || !std::isfinite(eps)) { pydem_set_error("pydem_fill_depressions: no automatic epsilon for max |z| = %g", amax); return -2; }
+        if (!(eps > 0) || !std::isfinite(eps)) { pydem_set_error("%s: no automatic epsilon for max |z| = %g", who, amax); return -2; }
     }
     if (eps > 0 && amax + eps == amax) {
-        pydem_set_error("pydem_fill_depressions: epsilon %g is not representable at the surface's magnitude (max |z| = %g)", eps, amax);
+        pydem_set_error("%s: epsilon %g is not representable at the surface's magnitude (max |z| = %g)", who, eps, amax);
         return -2;
     }
 
@@ -294,9 +294,27 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
         if (stamp < run) { converged = true; break; }       // the last pass enqueued changed nothing
     }
     if (!converged) {
-        pydem_set_error("pydem_fill_depressions: not converged after %lld passes (PYDEM_FILL_MAX_PASSES); the elevation is unchanged", (long long)run);
+        pydem_set_error("%s: not converged after %lld passes (PYDEM_FILL_MAX_PASSES); the elevation is unchanged", who, (long long)run);
         return -5;
     }
+    *epsilon = eps;
+    out->W = W; out->ctr = ctr; out->outlets = d_out; out->passes = stamp + 1;      // the passes that changed something and the one that found nothing to do
+    return 0;
+}
+
+// pydem_fill_depressions: the relaxation, then depth, counts and elev = W
+int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
+                           int64_t *passes, double *ms)
+{
+    ArenaLease lease;
+    PYDEM_TRY(arena_acquire(t->device, &lease));
+    FillRelax fr;
+    PYDEM_TRY(fill_relax(t, &lease, "pydem_fill_depressions", epsilon, outlets, t->ev[6], &fr));
+    double *W = fr.W;
+    unsigned long long *ctr = fr.ctr;
+    volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;
+    const double eps = *epsilon;
+    const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
     hipLaunchKernelGGL(k_fd_final, dim3(gcells), dim3(256), 0, t->stream, t->elev, W, t->NN, ctr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, FD_WORDS * 8, hipMemcpyDeviceToHost, t->stream));
@@ -304,9 +322,8 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     HIP_TRY(hipEventSynchronize(t->ev[7]));
     float el = 0.f;
     HIP_TRY(hipEventElapsedTime(&el, t->ev[6], t->ev[7]));
-    *epsilon = eps;
     if (ms) *ms = (double)el;
-    if (passes) *passes = stamp + 1;            // the passes that changed something and the one that found nothing to do
+    if (passes) *passes = fr.passes;
     if (n_raised) *n_raised = (int64_t)h[FD_RAISED];
     if (max_depth) *max_depth = as_double(h[FD_DEPTH]);
     if (eps > 0) { t->elev_f32 = false; t->elev_dtype = PYDEM_F64; }      // (eps == 0: every value of W is a value of z)

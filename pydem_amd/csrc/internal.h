@@ -137,6 +137,7 @@ struct pydem_tile {
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;
+    std::vector<pydem_depression> depr;     // the table of the last pydem_depressions (host memory; pydem_depressions_table copies it out)
     int64_t device_bytes = 0;
     pydem_timings tm = {};
 };
@@ -201,6 +202,12 @@ bool tile_line_watched(const pydem_tile *t, int axis, int64_t index);
 int stage_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double source_tol, int peaks, int pits, int artefacts_only);
 int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
                            int64_t *passes, double *ms);
+// the fill's relaxation alone (fill_depressions.hip): W at its fixed point in scratch of the caller's lease, the counter block
+// of the fill, the device copy of the outlets mask (null without one) and the passes it took
+struct FillRelax { double *W = nullptr; unsigned long long *ctr = nullptr; uint8_t *outlets = nullptr; int64_t passes = 0; };
+int fill_relax(pydem_tile *t, ArenaLease *lease, const char *who, double *epsilon, const uint8_t *outlets, hipEvent_t ev_start, FillRelax *out);
+int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
+                      int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms);
 int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);
 int stage_pit_candidates_read(pydem_tile *t, int64_t npits, int32_t *cells, double *elev);
 int stage_pit_paths(pydem_tile *t, const int32_t *order_host, int64_t npits, int max_iter, int max_dist, double max_dist_XY,

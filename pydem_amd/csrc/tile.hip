@@ -896,6 +896,26 @@ int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     return 0;
 }
 
+int pydem_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
+                      int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_depressions"));
+    t->depr.clear();
+    // reads the elevation and nothing else of the tile: no field, flag or pending edge delta changes
+    return stage_depressions(t, outlets, min_depth, min_cells, min_volume, label, n_found, n_kept, quanta, passes, ms);
+}
+
+int pydem_depressions_table(pydem_tile *t, int64_t rows, pydem_depression *table)
+{
+    if (rows != (int64_t)t->depr.size() || (rows > 0 && !table)) {
+        pydem_set_error("pydem_depressions_table: %lld rows asked, the last pydem_depressions kept %lld", (long long)rows, (long long)t->depr.size());
+        return -2;
+    }
+    if (rows > 0) memcpy(table, t->depr.data(), (size_t)rows * sizeof(pydem_depression));
+    return 0;
+}
+
 int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
 {
     HIP_TRY(hipSetDevice(t->device));

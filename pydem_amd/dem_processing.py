@@ -470,6 +470,75 @@ class DEMProcessor(object):
         self.fill_depressions_stats = stats
         return stats
 
+    depressions = None            # {'label', 'table'} of the last calc_depressions (no counterpart in the reference)
+    depressions_stats = None      # {'n_found', 'quanta', 'passes', 'ms'} of the last calc_depressions
+    kept_sinks = None             # (N, 2) int array: the outlets calc_fill_depressions_limited added
+
+    def _surface_on_host(self):
+        """True when the host twin must serve a call on the elevation: a dtype the device cannot hold, or a tile with fewer than
+        three rows or columns"""
+        elev = self._host.get('elev')
+        if elev is not None and (np.asarray(elev).dtype.kind not in 'iuf' or np.asarray(elev).ndim != 2):
+            return True
+        return min(self.shape) < 3
+
+    def calc_depressions(self, outlets=None, min_depth=0.0, min_cells=1, min_volume=0.0, return_labels=True):
+        """The depression inventory (closed-depression mapping; no reference method): W is the classic fill (epsilon 0) of the
+        elevation with the open cells of calc_fill_depressions -- border, neighbours of no-data cells, `outlets` (a boolean mask
+        of the tile's shape or a sequence of (row, col) pairs) -- and a depression is an 8-connected component of W > z, numbered
+        in ascending order of its first cell in raster order (include/pydem_hip.h: pydem_depressions).  Returns {'label', 'table'},
+        kept as `depressions`: the int32 label raster (0: in no kept depression, -1: no data; None without return_labels) and a
+        structured array with one row per depression: cells, bounding box r0 r1 c0 c1, spill_elev, bottom_row bottom_col
+        bottom_elev (the first of its lowest cells), max_depth, pour_row pour_col (the first of its sill cells: cells that are not
+        raised, touch the depression and lie at its spill elevation), n_sills, open_sill (1: a sill is an open cell, the lake may
+        be cut by the tile), area and volume (fixed-point sums with one result, in the units of dX * dY and z * dX * dY; their
+        quanta are in `depressions_stats`) and mean_depth = volume / area.  Depressions below min_depth, min_cells or min_volume
+        are dropped and the rest renumbered in the same order.  The elevation, its dtype and everything computed from it stay
+        as they are.  Per tile: a depression cut by the tile's border is open there; the nested hierarchy is not computed."""
+        from . import conditioning
+        lim = conditioning.depression_limits("calc_depressions", min_depth=min_depth, min_cells=min_cells, min_volume=min_volume)
+        if any(v is None for v in lim.values()):
+            raise ValueError("calc_depressions: min_depth, min_cells and min_volume must be numbers >= 0")
+        mask = None if outlets is None else self._outlets_mask(outlets)
+        if self._surface_on_host():
+            label, table, quanta = conditioning.label_depressions(self.elev, mask, lim['min_depth'], lim['min_cells'], lim['min_volume'],
+                                                                  self.dX2 * self.dY2)
+            stats = dict(n_found=None, quanta=quanta, passes=0, ms={})
+        else:
+            self._ensure_tile()
+            self._push('elev')
+            logger.info("Starting depression inventory")
+            label, rows, stats = self._tile.depressions(mask, lim['min_depth'], lim['min_cells'], lim['min_volume'], return_labels)
+            table = conditioning.depression_table(rows['cells'], rows['r0'], rows['r1'], rows['c0'], rows['c1'], rows['spill_elev'],
+                                                  rows['bottom'], rows['bottom_elev'], rows['pour'], rows['n_sills'], rows['open_sill'],
+                                                  rows['area'], rows['volume'], self.shape[1])
+        self.depressions = dict(label=label if return_labels else None, table=table)
+        self.depressions_stats = stats
+        return self.depressions
+
+    def calc_fill_depressions_limited(self, max_depth=None, max_cells=None, max_volume=None, epsilon=None, outlets=None, max_rounds=64):
+        """The z-limit fill (ArcGIS Fill's z-limit, WhiteboxTools' max_depth): a depression deeper than max_depth, with more than
+        max_cells cells or more than max_volume of volume is kept as a sink; everything else is filled, the shallow depressions
+        nested inside a kept one included.  A loop over calc_depressions and calc_fill_depressions: the inventory is taken with
+        the outlets collected so far, the bottoms of the depressions over a limit join the outlets (each round adds at least
+        one), and when none is over a limit calc_fill_depressions(epsilon, outlets=collected) runs once.  The outlets the loop
+        added are kept as `kept_sinks`, an (N, 2) int array.  RuntimeError after max_rounds rounds: the elevation is then
+        untouched.  With no limit it is calc_fill_depressions.  Returns the filled elevation."""
+        from . import conditioning
+        lim = conditioning.depression_limits("calc_fill_depressions_limited", max_depth=max_depth, max_cells=max_cells, max_volume=max_volume)
+        mask = None if outlets is None else self._outlets_mask(outlets)
+        if all(v is None for v in lim.values()):
+            self.kept_sinks = np.zeros((0, 2), np.int64)
+            return self.calc_fill_depressions(epsilon, mask)
+        before = self.depressions, self.depressions_stats
+        try:
+            mask, kept = conditioning.limited_outlets(lambda o: self.calc_depressions(o, return_labels=False)['table'], tuple(self.shape),
+                                                      mask, lim['max_depth'], lim['max_cells'], lim['max_volume'], max_rounds)
+        finally:
+            self.depressions, self.depressions_stats = before
+        self.kept_sinks = kept
+        return self.calc_fill_depressions(epsilon, mask)
+
     def calc_slopes_directions(self, plotflag=False):
         """Slope magnitude and D-infinity direction (reference :587-619)."""
         self.run_slopes_directions()
