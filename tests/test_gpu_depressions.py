@@ -8,6 +8,7 @@ import pytest
 
 import depression_fields as D
 import fill_fields as F
+from depression_checks import same
 
 pytestmark = pytest.mark.gpu
 
@@ -39,18 +40,6 @@ def device(name, z, outlets=None, **kw):
     dp = DEMProcessor(elev=z, **D.spacing_kwargs(name))
     res = dp.calc_depressions(outlets, **kw)
     return dp, res
-
-
-def same(res, want, stats=None):
-    label, table, quanta = want
-    assert res['label'].dtype == np.int32 and np.array_equal(res['label'], label)
-    assert res['table'].dtype == table.dtype and len(res['table']) == len(table)
-    for col in table.dtype.names:
-        assert np.array_equal(res['table'][col], table[col]), col
-    for col in ('area', 'volume', 'spill_elev', 'max_depth', 'mean_depth'):
-        assert res['table'][col].tobytes() == table[col].tobytes(), col
-    if stats is not None:
-        assert stats['quanta'] == quanta
 
 
 # 1. device against host twin
