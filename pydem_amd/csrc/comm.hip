@@ -220,7 +220,9 @@ int pydem_comm_put(pydem_comm *c, const double *host_in, int64_t n_doubles, int6
 // of the strips) into a few words per tile, the only thing the host reads per wave.
 // The rules are those of pydem_amd/process_manager.py (_edge_inputs, _todo_dropped, _adopt_finished,
 // _tile_metric), which stays the specification: the CPU test tier runs it with the oracle-backed processor
-// and tests/test_gpu_process_manager.py checks that both produce the same waves, rounds and masks.
+// and tests/test_gpu_process_manager.py checks that both produce the same waves, rounds and masks;
+// tests/test_gpu_board_eval.py and tests/test_gpu_board_schedule.py call those functions on hand-made boards and
+// compare the kernels below with them number by number.
 struct pydem_board_desc {           // one per tile; offsets in doubles into the board, -1 = no such line
     int32_t n, m;
     int64_t own_todo[4], own_done[4];             // sides: left, right, top, bottom
@@ -320,23 +322,34 @@ __global__ __launch_bounds__(1024) void k_board_eval(const double *__restrict__ 
         const bool nb_td = rd(D.nb_todo[k], p) != 0.0;
         bool done = nb_dn;
         // ---- corner rules (:258-270): the top / bottom strip gives its corner up when both strips are finished
-        // there; with a one-pixel overlap both take the diagonal neighbour's value when that one is finished
+        // there; with a one-pixel overlap both take the diagonal neighbour's value when that one is finished.
+        // The host applies the four rules one after the other, in the order tl, br, tr, bl, and a rule sees what the
+        // earlier ones did to the top / bottom strip.  With two or more rows and columns every end cell belongs to
+        // one rule; in a 1-wide (1-high) tile both ends of the top and bottom (left and right) strips are ONE cell
+        // (index -1 is index 0), so an end cell replays all four rules on the end cells: a strip that gave its
+        // corner up to an earlier rule is no longer finished for a later one, and the last hand-over sets the value.
         const bool at_lo = p == 0, at_hi = p == len - 1;
-        int ctb = -1, clr = -1;
         if (at_lo || at_hi) {
-            if (k >= 2) { ctb = k; clr = at_lo ? 0 : 1; }
-            else { clr = k; ctb = at_lo ? 2 : 3; }
-        }
-        // (a 1-wide or 1-high tile has both ends in one position: the lower end's rule wins like the dict order)
-        if (ctb >= 0) {
-            const int64_t pos_tb = clr == 0 ? 0 : m - 1;      // corner on the top / bottom strip
-            const int64_t pos_lr = ctb == 2 ? 0 : n - 1;      // corner on the left / right strip
-            const bool d_tb = rd(D.nb_done[ctb], pos_tb) != 0.0;
-            const bool d_lr = rd(D.nb_done[clr], pos_lr) != 0.0;
-            if (d_tb && d_lr) {
-                if (k >= 2) done = false;                                                           // :266
-                const int key = (ctb == 2 ? 0 : 2) + (clr == 0 ? 0 : 1);                            // tl, tr, bl, br
-                if (D.cnr_1ov[key] && D.cnr_done[key] >= 0 && mb[D.cnr_done[key]] != 0.0) data = mb[D.cnr_uca[key]];   // :268-270
+            const int hi_tb = m == 1 ? 0 : 1;                      // bit of a top / bottom strip's upper end (its only cell: bit 0)
+            unsigned fin = 0;                                      // bit (strip - 2) * 2 + end: that end of top / bottom is still finished
+            for (int tb = 2; tb < 4; tb++) {
+                if (rd(D.nb_done[tb], 0) != 0.0) fin |= 1u << ((tb - 2) * 2);
+                if (rd(D.nb_done[tb], m - 1) != 0.0) fin |= 1u << ((tb - 2) * 2 + hi_tb);
+            }
+#pragma unroll 1
+            for (int r = 0; r < 4; r++) {
+                const int key = r == 0 ? 0 : r == 1 ? 3 : r == 2 ? 1 : 2;                           // tl, br, tr, bl as (tl, tr, bl, br)[key]
+                const int tb = 2 + (key >> 1), lr = key & 1;
+                const int64_t pos_tb = lr == 0 ? 0 : m - 1;       // corner on the top / bottom strip
+                const int64_t pos_lr = tb == 2 ? 0 : n - 1;       // corner on the left / right strip
+                const unsigned bit = 1u << ((tb - 2) * 2 + (lr == 0 ? 0 : hi_tb));
+                if ((fin & bit) && rd(D.nb_done[lr], pos_lr) != 0.0) {
+                    fin &= ~bit;
+                    const bool mine_tb = k == tb && p == pos_tb, mine_lr = k == lr && p == pos_lr;
+                    if (mine_tb) done = false;                                                      // :266
+                    if ((mine_tb || mine_lr) && D.cnr_1ov[key] && D.cnr_done[key] >= 0 && mb[D.cnr_done[key]] != 0.0)
+                        data = mb[D.cnr_uca[key]];                                                  // :268-270
+                }
             }
         }
         // ---- rule :274 (full), or only where the neighbour line is the tile's own (mosaic border)
@@ -364,17 +377,43 @@ __global__ __launch_bounds__(1024) void k_board_eval(const double *__restrict__ 
                 a_ndone += own_td && edn2; a_pdone += own_td;
             }
         }
-        // ---- dropped 'todo' pixels (_todo_dropped): a corner pixel survives if either of its strips keeps it
-        if (k < 2 || !(at_lo || at_hi)) {
-            bool keep_s = own_td && !drop_self, keep_f = own_td && !drop_full;
-            if (k < 2 && (at_lo || at_hi)) {
-                const int64_t pos_tb = k == 0 ? 0 : m - 1;
-                const bool tb_own = rd(D.own_todo[ctb], pos_tb) != 0.0, tb_nb = rd(D.nb_todo[ctb], pos_tb) != 0.0;
-                keep_s = keep_s || (tb_own && !(tb_nb && D.nb_self[ctb]));
-                keep_f = keep_f || (tb_own && !tb_nb);
+        // ---- dropped 'todo' pixels (_todo_dropped): a corner pixel survives if either of its strips keeps it.  Away from
+        // the strip ends a pixel is lost when its flag is dropped.  The (up to) eight end cells are counted by the
+        // tile's first thread, the way the host counts them: the corners tl, tr, bl, br one after the other share what
+        // their two strips keep (in a 1-wide or 1-high tile both ends of a strip are one cell, so what one corner
+        // shares reaches the next), every lost end cell counts once per strip and a corner lost on both strips once less.
+        if (!(at_lo || at_hi)) { a_dself += drop_self; a_dfull += drop_full; }
+        if (q == 0) {
+            const int hi_lr = n == 1 ? 0 : 1, hi_tb = m == 1 ? 0 : 1;
+            unsigned own = 0, keep_s = 0, keep_f = 0;              // bit strip * 2 + end
+#pragma unroll 1
+            for (int s = 0; s < 4; s++)
+#pragma unroll 1
+                for (int e = 0; e < 2; e++) {
+                    const int64_t pos = e == 0 ? 0 : (s < 2 ? n : m) - 1;
+                    const unsigned bit = 1u << (s * 2 + (e == 0 ? 0 : (s < 2 ? hi_lr : hi_tb)));
+                    const bool o = rd(D.own_todo[s], pos) != 0.0, t = rd(D.nb_todo[s], pos) != 0.0;
+                    if (o) own |= bit;
+                    if (o && !(t && D.nb_self[s])) keep_s |= bit;
+                    if (o && !t) keep_f |= bit;
+                }
+            unsigned pair[4];                                      // the two cells of the corners tl, tr, bl, br
+            for (int c = 0; c < 4; c++) {
+                const int tb = 2 + (c >> 1), lr = c & 1;
+                pair[c] = (1u << (lr * 2 + (tb == 2 ? 0 : hi_lr))) | (1u << (tb * 2 + (lr == 0 ? 0 : hi_tb)));
             }
-            a_dself += own_td && !keep_s;
-            a_dfull += own_td && !keep_f;
+            for (int c = 0; c < 4; c++) {
+                if (keep_s & pair[c]) keep_s |= pair[c];
+                if (keep_f & pair[c]) keep_f |= pair[c];
+            }
+            const unsigned lost_s = own & ~keep_s, lost_f = own & ~keep_f;
+            int c_s = __popc(lost_s), c_f = __popc(lost_f);
+            for (int c = 0; c < 4; c++) {
+                c_s -= (lost_s & pair[c]) == pair[c];
+                c_f -= (lost_f & pair[c]) == pair[c];
+            }
+            a_dself += (unsigned long long)c_s;
+            a_dfull += (unsigned long long)c_f;
         }
         unsigned long long h = (unsigned long long)__double_as_longlong(done ? data : 0.0);
         h = mix64(h ^ ((unsigned long long)q * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)done << 1) ^ (unsigned long long)td_adopt);
