@@ -159,6 +159,19 @@ def check(rc):
         raise HipError("libpydem_hip error %d: %s" % (rc, load().pydem_hip_last_error().decode()))
 
 
+def _ptr(a):
+    """The array's buffer as a void* argument; None is the null pointer."""
+    return a.ctypes.data_as(_P) if a is not None else None
+
+
+def _sweep(fn, *args):
+    """One flow-graph sweep export, whose last three parameters are double *ms, int64_t *levels, int64_t *n_unresolved:
+    (device ms, levels, unresolved cells)."""
+    ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
+    check(fn(*(args + (C.byref(ms), C.byref(levels), C.byref(left)))))
+    return ms.value, int(levels.value), int(left.value)
+
+
 def device_count():
     n = C.c_int(0)
     check(load().pydem_hip_device_count(C.byref(n)))
@@ -196,6 +209,20 @@ class Tile(object):
             self.close()
         except Exception:
             pass
+
+    def _mask(self, a, what):
+        """`a` as a uint8 mask (nonzero: set) of the tile's shape"""
+        mask = np.ascontiguousarray(np.asarray(a) != 0, np.uint8)
+        if mask.shape != self.shape:
+            raise ValueError("%s of shape %r for a tile of shape %r" % (what, mask.shape, self.shape))
+        return mask
+
+    def _plane(self, a, what):
+        """`a` as a float64 plane of the tile's shape"""
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != self.shape:
+            raise ValueError("%s of shape %r for a tile of shape %r" % (what, a.shape, self.shape))
+        return a
 
     def set_spacing(self, dX, dY, dX2, dY2):
         arrs = [np.ascontiguousarray(a, np.float64) for a in (dX, dY, dX2, dY2)]
@@ -268,15 +295,10 @@ class Tile(object):
         """pydem_fill_depressions on the resident elevation: (depth or None, epsilon used, raised cells, maximum depth, passes,
         device ms).  epsilon: None (or < 0) is automatic; outlets: a mask of the tile's shape or None."""
         eps = C.c_double(-1.0 if epsilon is None else float(epsilon))
-        mask = None
-        if outlets is not None:
-            mask = np.ascontiguousarray(np.asarray(outlets) != 0, np.uint8)
-            if mask.shape != self.shape:
-                raise ValueError("outlets mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        mask = None if outlets is None else self._mask(outlets, 'outlets mask')
         depth = np.empty(self.shape, np.float64) if want_depth else None
         raised, dmax, passes, ms = C.c_int64(0), C.c_double(0), C.c_int64(0), C.c_double(0)
-        check(self.lib.pydem_fill_depressions(self._h, C.byref(eps), mask.ctypes.data_as(_P) if mask is not None else None,
-                                              depth.ctypes.data_as(_P) if want_depth else None, C.byref(raised), C.byref(dmax),
+        check(self.lib.pydem_fill_depressions(self._h, C.byref(eps), _ptr(mask), _ptr(depth), C.byref(raised), C.byref(dmax),
                                               C.byref(passes), C.byref(ms)))
         return depth, eps.value, int(raised.value), dmax.value, int(passes.value), ms.value
 
@@ -288,17 +310,12 @@ class Tile(object):
     def depressions(self, outlets=None, min_depth=0.0, min_cells=1, min_volume=0.0, want_labels=True):
         """pydem_depressions on the resident elevation: (label raster or None, rows (DEPRESSION_ROW), info) with info =
         {'n_found', 'quanta': (area, volume), 'passes', 'ms': {part: device ms}}.  outlets: a mask of the tile's shape or None."""
-        mask = None
-        if outlets is not None:
-            mask = np.ascontiguousarray(np.asarray(outlets) != 0, np.uint8)
-            if mask.shape != self.shape:
-                raise ValueError("outlets mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        mask = None if outlets is None else self._mask(outlets, 'outlets mask')
         label = np.empty(self.shape, np.int32) if want_labels else None
         found, kept, passes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         quanta, ms = np.zeros(2), np.zeros(len(self.DEPRESSION_PARTS))
-        check(self.lib.pydem_depressions(self._h, mask.ctypes.data_as(_P) if mask is not None else None, float(min_depth), int(min_cells),
-                                         float(min_volume), label.ctypes.data_as(_P) if want_labels else None, C.byref(found),
-                                         C.byref(kept), quanta.ctypes.data_as(_P), C.byref(passes), ms.ctypes.data_as(_P)))
+        check(self.lib.pydem_depressions(self._h, _ptr(mask), float(min_depth), int(min_cells), float(min_volume), _ptr(label),
+                                         C.byref(found), C.byref(kept), _ptr(quanta), C.byref(passes), _ptr(ms)))
         rows = np.zeros(int(kept.value), self.DEPRESSION_ROW)
         check(self.lib.pydem_depressions_table(self._h, int(kept.value), rows.ctypes.data_as(_P)))
         return label, rows, dict(n_found=int(found.value), quanta=(float(quanta[0]), float(quanta[1])), passes=int(passes.value),
@@ -346,26 +363,15 @@ class Tile(object):
         """pydem_dist_down on the tile's flow graph: (float64 [n, m], device ms, levels, unresolved cells).  `target`: a mask
         of the tile's shape, or None with `uca_threshold`.  download=False: the sweep alone (None instead of the array)."""
         out = np.empty(self.shape, np.float64) if download else None
-        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        mask = None
-        if target is not None:
-            mask = np.ascontiguousarray(np.asarray(target) != 0, np.uint8)
-            if mask.shape != self.shape:
-                raise ValueError("target mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
-        check(self.lib.pydem_dist_down(self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat],
-                                       mask.ctypes.data_as(_P) if mask is not None else None,
-                                       float(uca_threshold) if mask is None else 0.0, out.ctypes.data_as(_P) if download else None,
-                                       C.byref(ms), C.byref(levels), C.byref(left)))
-        return out, ms.value, int(levels.value), int(left.value)
+        mask = None if target is None else self._mask(target, 'target mask')
+        return (out,) + _sweep(self.lib.pydem_dist_down, self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat], _ptr(mask),
+                               float(uca_threshold) if mask is None else 0.0, _ptr(out))
 
     def dist_up(self, kind, stat, edge_nan=True, download=True):
         """pydem_dist_up on the tile's flow graph: (float64 [n, m], device ms, levels, unresolved cells).  download=False: the
         sweep alone (None instead of the array)."""
         out = np.empty(self.shape, np.float64) if download else None
-        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        check(self.lib.pydem_dist_up(self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat], int(bool(edge_nan)),
-                                     out.ctypes.data_as(_P) if download else None, C.byref(ms), C.byref(levels), C.byref(left)))
-        return out, ms.value, int(levels.value), int(left.value)
+        return (out,) + _sweep(self.lib.pydem_dist_up, self._h, self.DIST_KINDS[kind], self.DIST_STATS[stat], int(bool(edge_nan)), _ptr(out))
 
     REV_OPS = {'sum': 0, 'max': 1}
 
@@ -374,40 +380,21 @@ class Tile(object):
         'max' / 1; seed: float64 of the tile's shape or None (0 everywhere); absorb: a mask of the tile's shape or None.
         download=False: the sweep alone (None instead of the array)."""
         out = np.empty(self.shape, np.float64) if download else None
-        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        sd = mask = None
-        if seed is not None:
-            sd = np.ascontiguousarray(seed, np.float64)
-            if sd.shape != self.shape:
-                raise ValueError("seed of shape %r for a tile of shape %r" % (sd.shape, self.shape))
-        if absorb is not None:
-            mask = np.ascontiguousarray(np.asarray(absorb) != 0, np.uint8)
-            if mask.shape != self.shape:
-                raise ValueError("absorb mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
-        check(self.lib.pydem_rev_accum(self._h, int(self.REV_OPS.get(op, op)), sd.ctypes.data_as(_P) if sd is not None else None,
-                                       mask.ctypes.data_as(_P) if mask is not None else None, float(absorb_value),
-                                       out.ctypes.data_as(_P) if download else None, C.byref(ms), C.byref(levels), C.byref(left)))
-        return out, ms.value, int(levels.value), int(left.value)
+        sd = None if seed is None else self._plane(seed, 'seed')
+        mask = None if absorb is None else self._mask(absorb, 'absorb mask')
+        return (out,) + _sweep(self.lib.pydem_rev_accum, self._h, int(self.REV_OPS.get(op, op)), _ptr(sd), _ptr(mask), float(absorb_value),
+                               _ptr(out))
 
     def fwd_accum(self, load, mult=None, cap=None, edge_nan=True, inflow=False, download=True):
         """pydem_fwd_accum on the tile's flow graph: (float64 [n, m], inflow [n, m] or None, device ms, levels, unresolved
         cells).  load: float64 of the tile's shape; mult, cap: the same or None.  inflow: bring the inflow plane back too.
         download=False: the sweep alone (None instead of the arrays; the inflow pass still runs if asked for)."""
         out = np.empty(self.shape, np.float64) if download else None
-        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        planes = []
-        for name, a in (('load', load), ('mult', mult), ('cap', cap)):
-            if a is not None:
-                a = np.ascontiguousarray(a, np.float64)
-                if a.shape != self.shape:
-                    raise ValueError("%s of shape %r for a tile of shape %r" % (name, a.shape, self.shape))
-            planes.append(a)
+        planes = [None if a is None else self._plane(a, name) for name, a in (('load', load), ('mult', mult), ('cap', cap))]
         # (download=False with inflow: the pass runs and its plane comes back -- the C-ABI has no other way to ask for it)
         flow = np.empty(self.shape, np.float64) if inflow else None
-        ptr = lambda a: a.ctypes.data_as(_P) if a is not None else None
-        check(self.lib.pydem_fwd_accum(self._h, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), int(bool(edge_nan)), ptr(out), ptr(flow),
-                                       C.byref(ms), C.byref(levels), C.byref(left)))
-        return out, flow, ms.value, int(levels.value), int(left.value)
+        return (out, flow) + _sweep(self.lib.pydem_fwd_accum, self._h, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]),
+                                    int(bool(edge_nan)), _ptr(out), _ptr(flow))
 
     TREE_OPS = {'sum': 0, 'max': 1, 'min': 2}
 
@@ -416,14 +403,8 @@ class Tile(object):
         unresolved cells).  load: float64 of the tile's shape; op: 'sum' / 0, 'max' / 1 or 'min' / 2.  The accumulation is cut at
         the link boundaries exactly when a stream set is given: `streams`, a mask of the tile's shape, or `uca_threshold`.
         download=False: the sweep (and the gather) alone, None instead of the plane."""
-        ld = np.ascontiguousarray(load, np.float64)
-        if ld.shape != self.shape:
-            raise ValueError("load of shape %r for a tile of shape %r" % (ld.shape, self.shape))
-        mask = None
-        if streams is not None:
-            mask = np.ascontiguousarray(np.asarray(streams) != 0, np.uint8)
-            if mask.shape != self.shape:
-                raise ValueError("stream mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
+        ld = self._plane(load, 'load')
+        mask = None if streams is None else self._mask(streams, 'stream mask')
         cut = mask is not None or uca_threshold is not None
         out = np.empty(self.shape, np.float64) if download else None
         cells = vals = None
@@ -433,13 +414,9 @@ class Tile(object):
                 raise ValueError("`at` holds cells outside the int32 range")
             cells = np.ascontiguousarray(cells.ravel(), np.int32)
             vals = np.empty(cells.size, np.float64)
-        ms, levels, left = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        ptr = lambda a: a.ctypes.data_as(_P) if a is not None else None
-        check(self.lib.pydem_tree_accum(self._h, int(self.TREE_OPS.get(op, op)), ptr(ld), int(cut), ptr(mask),
-                                        float(uca_threshold) if mask is None and uca_threshold is not None else 0.0,
-                                        int(bool(edge_nan)), ptr(out), ptr(cells), cells.size if cells is not None else 0, ptr(vals),
-                                        C.byref(ms), C.byref(levels), C.byref(left)))
-        return out, vals, ms.value, int(levels.value), int(left.value)
+        return (out, vals) + _sweep(self.lib.pydem_tree_accum, self._h, int(self.TREE_OPS.get(op, op)), _ptr(ld), int(cut), _ptr(mask),
+                                    float(uca_threshold) if mask is None and uca_threshold is not None else 0.0,
+                                    int(bool(edge_nan)), _ptr(out), _ptr(cells), cells.size if cells is not None else 0, _ptr(vals))
 
     def stream_network(self, streams=None, uca_threshold=None, receiver=True, order=True, link=True, basin=True):
         """pydem_stream_network on the tile's flow graph: ({'receiver', 'order', 'link', 'basin'}: int32 [n, m] or None, device ms
@@ -449,16 +426,11 @@ class Tile(object):
         want = dict(receiver=receiver, order=order, link=link, basin=basin)
         planes = {k: np.empty(self.shape, np.int32) if v else None for k, v in want.items()}
         ms, levels, left = (C.c_double * 3)(), (C.c_int64 * 2)(), (C.c_int64 * 2)()
-        mask = None
-        if streams is not None:
-            mask = np.ascontiguousarray(np.asarray(streams) != 0, np.uint8)
-            if mask.shape != self.shape:
-                raise ValueError("stream mask of shape %r for a tile of shape %r" % (mask.shape, self.shape))
-        elif uca_threshold is None and (order or link or basin):
+        mask = None if streams is None else self._mask(streams, 'stream mask')
+        if mask is None and uca_threshold is None and (order or link or basin):
             raise ValueError("order, link and basin need a stream mask or a uca_threshold")
-        ptr = lambda a: a.ctypes.data_as(_P) if a is not None else None
-        check(self.lib.pydem_stream_network(self._h, ptr(mask), float(uca_threshold) if mask is None and uca_threshold is not None else 0.0,
-                                            ptr(planes['receiver']), ptr(planes['order']), ptr(planes['link']), ptr(planes['basin']),
+        check(self.lib.pydem_stream_network(self._h, _ptr(mask), float(uca_threshold) if mask is None and uca_threshold is not None else 0.0,
+                                            _ptr(planes['receiver']), _ptr(planes['order']), _ptr(planes['link']), _ptr(planes['basin']),
                                             ms, levels, left))
         return planes, tuple(ms), tuple(int(v) for v in levels), tuple(int(v) for v in left)
 

@@ -66,10 +66,10 @@ def test_unknown_kind_or_statistic_is_refused_before_device_work(kw):
 def test_masked_target_counts_masked_cells_as_not_target():
     dp = _dp()
     t = np.ma.masked_array(np.ones((5, 5), bool), mask=np.eye(5, dtype=bool))
-    mask, thr = dp._dist_down_target(t, None, 'h', 'ave')
+    mask, thr = dp._stream_set(t, None)
     assert thr is None and mask.dtype == bool and mask.shape == (5, 5)
     assert not np.diag(mask).any() and mask.sum() == 20
-    mask, thr = dp._dist_down_target(None, 0, 'v', 'max')             # a threshold of zero is a threshold
+    mask, thr = dp._stream_set(None, 0)                               # a threshold of zero is a threshold
     assert mask is None and thr == 0.0
 
 

@@ -6,12 +6,13 @@ Kahn reference of tests/test_dist_down_ref.py on the oracle's graphs, cell by ce
 the bound tests/test_gpu_weighted_uca.py uses for re-associated sums on this graph.  Threshold targets are evaluated on the
 device's own uca (that is the call's definition), so the reference gets `dp.uca >= threshold` as its mask.  Then: what the
 call must leave alone, run-to-run identity and the memory it holds."""
-import functools
 import warnings
 
 import numpy as np
 import pytest
 
+from flowgraph_kit import (_same_snapshot, _snapshot, _strips, assert_same_bits, circular_case, nan_speck_pair, pair, run_child,
+                           shared_deep_pair as deep_pair, shared_fractal_pair as fractal_pair)
 from test_dist_down_ref import KINDS, STATS, dist_down_ref
 
 pytestmark = pytest.mark.gpu
@@ -38,12 +39,6 @@ def compare(dev, o, target, kind, stat, what, min_finite=None):
     assert np.array_equal(np.isnan(dev), nan_ref), "%s: NaN patterns differ (%d device, %d reference)" % (what, np.isnan(dev).sum(), nan_ref.sum())
     assert (err <= lim).all(), "%s: %d cells off, worst %.3g of the scale" % (what, (err > lim).sum(), worst)
     return ref, final, depth
-
-
-@functools.lru_cache(maxsize=None)
-def fractal_pair(shape, seed):
-    from test_gpu_weighted_uca import fractal_pair as make
-    return make(shape, seed)
 
 
 FRACTALS = [((300, 260), 5), ((700, 520), 41), ((1024, 1024), 42)]
@@ -80,23 +75,6 @@ def test_every_kind_and_statistic(kind, stat, cells):
     compare(d, o, target, kind, stat, '%s/%s %d cells' % (kind, stat, cells), min_finite=0.85)
 
 
-@functools.lru_cache(maxsize=None)
-def deep_pair():
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor
-    n, m = 900, 600
-    row, col = np.arange(n, dtype=np.float64)[:, None], np.arange(m, dtype=np.float64)[None, :]
-    z = 2000 - 1.5 * row + 10 * np.sin(col / 37) * row / n + np.random.default_rng(1).normal(0, 0.4, (n, m))
-    o = O.OracleDEM(z, dX=30.0, dY=30.0, drain_pits=True)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        dp.calc_uca()
-    return o, dp
-
-
 @pytest.mark.parametrize('stat', STATS)
 def test_deep_ramp_to_the_last_two_rows(stat):
     """a 900-row ramp with the target at its foot: the reverse depth is the tile's length, not a hillslope's"""
@@ -112,7 +90,6 @@ def test_deep_ramp_to_the_last_two_rows(stat):
 
 @pytest.mark.parametrize('loop', ['two_cells', 'three_cells', 'two_loops'])
 def test_circular_drainage_is_nan_and_counted(loop):
-    from test_gpu_weighted_uca import circular_case
     o, dp = circular_case(loop)
     n, m = dp.shape
     target = np.zeros((n, m), bool)
@@ -126,19 +103,8 @@ def test_circular_drainage_is_nan_and_counted(loop):
 
 
 def test_nan_specks():
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor, synth
-    z = synth.fractal(640, 700, seed=7, top_shift=7, n_octaves=7)
-    rng = np.random.default_rng(3)
-    z[rng.integers(0, 640, 40), rng.integers(0, 700, 40)] = np.nan
-    z[0, 5] = np.nan; z[639, 300] = np.nan; z[200, 0] = np.nan
-    o = O.OracleDEM(z, dX=30.0, dY=30.0, drain_pits=True)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        uca = np.array(dp.calc_uca())
+    z, o, dp, _ = nan_speck_pair((640, 700), 40, [(0, 5), (639, 300), (200, 0)])
+    uca = np.array(dp.uca)
     assert np.isnan(uca).any()
     thr = 200 * CELL
     target = uca >= thr
@@ -151,19 +117,12 @@ def test_nan_specks():
 
 def test_row_varying_spacing():
     import capacity_terrain as CT
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor, synth
+    from pydem_amd import synth
     n, m = 333, 290
     z = synth.fractal(n, m, seed=19, top_shift=7, n_octaves=7)
     dX, dY = CT.spacing(n, seed=4)
     sp = dict(dX=dX, dY=dY, dX2=np.r_[dX, dX[-1]] + 0.003, dY2=np.r_[dY[0], dY] - 0.007)
-    o = O.OracleDEM(z, drain_pits=True, **sp)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, fill_flats=False, drain_pits_path=False, drain_pits=True, **sp)
-        dp.calc_slopes_directions()
-        dp.calc_uca()
+    o, dp = pair(z, **sp)
     thr = 150 * 25.0 * 31.0
     target = np.asarray(dp.uca) >= thr
     for kind, stat in (('h', 'ave'), ('s', 'ave'), ('h', 'max'), ('v', 'min')):
@@ -208,7 +167,6 @@ def check_schedules():
     target[-2:] = True
     compare(dp.calc_dist_down(target=target), o, target, 'h', 'ave', 'schedule deep ramp', 0.60)
     levels.append(dp.dist_down_stats['levels'])
-    from test_gpu_weighted_uca import circular_case
     o, dp = circular_case('two_loops')
     target = np.zeros(dp.shape, bool)
     target[-1, -1] = True
@@ -220,7 +178,6 @@ def check_schedules():
 @pytest.mark.parametrize('env', [{'PYDEM_DIST_PASSES': '0'}, {'PYDEM_DIST_MIN_PER_VISIT': '0'}, {'PYDEM_DIST_PASSES': '2'}])
 def test_schedules(env):
     """the queue alone, tile passes to the end, two passes then the queue (the switches are read once per process)"""
-    from test_gpu_weighted_uca import run_child
     r = run_child("from test_gpu_dist_down import check_schedules\nprint('LEVELS', check_schedules())\nprint('CHILD-OK')", env=env, timeout=300)
     levels = eval(r.stdout.split('LEVELS', 1)[1].splitlines()[0])
     if env.get('PYDEM_DIST_PASSES') == '0':
@@ -229,36 +186,7 @@ def test_schedules(env):
         assert levels[0] < 70 and levels[1] < 927, levels       # a pass finishes whole chains inside a tile, not one cell of each
 
 
-def _held_fields(dp):
-    """every field of the tile that can be downloaded, by field id"""
-    from pydem_amd import _ffi
-    out = {}
-    for f in range(12):
-        try:
-            out[f] = dp._tile.download(f)
-        except _ffi.HipError:
-            pass
-    return out
-
-
-def _snapshot(dp):
-    return _held_fields(dp), dp._tile.graph_words(), dp._tile.pit_edges(), dp.timings
-
-
-def _same_snapshot(a, b):
-    fa, ga, pa, ta = a
-    fb, gb, pb, tb = b
-    assert sorted(fa) == sorted(fb)
-    for f in fa:
-        assert fa[f].tobytes() == fb[f].tobytes(), "field %d changed" % f
-    assert np.array_equal(ga, gb)
-    for x, y in zip(pa, pb):
-        assert x.tobytes() == y.tobytes()
-    assert ta == tb, [(k, ta[k], tb[k]) for k in ta if ta[k] != tb[k]]
-
-
 def test_state_integrity():
-    from test_gpu_weighted_uca import _strips, assert_bitwise
     from pydem_amd import DEMProcessor, synth
     z = synth.fractal(520, 700, seed=11, top_shift=7, n_octaves=7)
     kw = dict(dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
@@ -281,7 +209,7 @@ def test_state_integrity():
                 assert np.isfinite(a).any() and np.isfinite(b).any() and not np.array_equal(a, b, equal_nan=True)
                 _same_snapshot(before, _snapshot(dp))
                 uca = np.array(dp.uca)
-                assert_bitwise(dp.calc_weighted_uca(1.0), uca, 'w = 1 after the distance calls')
+                assert_same_bits(dp.calc_weighted_uca(1.0), uca, 'w = 1 after the distance calls')
                 dp.calc_dist_down(uca_threshold=300 * CELL)
             f0 = {k: np.array(getattr(dp, k)) for k in ('uca', 'edge_todo', 'edge_done')}
             dp.calc_uca(uca_init=f0['uca'], edge_init_data=strips)

@@ -6,12 +6,13 @@ tests/test_dist_up_ref.py on the oracle's graphs, cell by cell:
 the bound and the form of tests/test_gpu_dist_down.py.  Then the schedules (bit-identical), what the call must leave alone,
 run-to-run identity and the memory it holds."""
 import functools
-import hashlib
 import warnings
 
 import numpy as np
 import pytest
 
+from flowgraph_kit import (_same_snapshot, _snapshot, bits, circular_case, nan_speck_pair, pair, run_child, shared_deep_pair as deep_pair,
+                           shared_fractal_pair as fractal_pair)
 from test_dist_down_ref import KINDS, STATS
 from test_dist_up_ref import dist_up_ref, edge_nan_cells
 
@@ -37,30 +38,6 @@ def compare(dev, o, kind, stat, edge_nan, what, min_finite=None):
     assert np.array_equal(np.isnan(dev), nan_ref), "%s: NaN patterns differ (%d device, %d reference)" % (what, np.isnan(dev).sum(), nan_ref.sum())
     assert (err <= lim).all(), "%s: %d cells off, worst %.3g of the scale" % (what, (err > lim).sum(), worst)
     return ref, final, depth
-
-
-def bits(a):
-    return hashlib.sha256(np.ascontiguousarray(a, np.float64).tobytes()).hexdigest()
-
-
-@functools.lru_cache(maxsize=None)
-def fractal_pair(shape, seed):
-    from test_gpu_weighted_uca import fractal_pair as make
-    return make(shape, seed)
-
-
-def pair(z, drain_pits=True, **spacing):
-    """(oracle after calc_uca, device processor after calc_uca) on the elevation z"""
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor
-    o = O.OracleDEM(z, drain_pits=drain_pits, **spacing)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, fill_flats=False, drain_pits_path=False, drain_pits=drain_pits, **spacing)
-        dp.calc_slopes_directions()
-        dp.calc_uca()
-    return o, dp
 
 
 FRACTALS = [((300, 260), 5), ((700, 520), 41), ((1024, 1024), 42)]
@@ -90,12 +67,6 @@ def test_every_kind_and_statistic(kind, stat):
 
 
 @functools.lru_cache(maxsize=None)
-def deep_pair():
-    from test_gpu_dist_down import deep_pair as make
-    return make()
-
-
-@functools.lru_cache(maxsize=None)
 def deep_ramp_depth():
     return dist_up_ref(deep_pair()[0], 'h', 'max', False)[2]
 
@@ -113,7 +84,6 @@ def test_deep_ramp(stat):
 
 @pytest.mark.parametrize('loop', ['two_cells', 'three_cells', 'two_loops'])
 def test_circular_drainage_is_nan_and_counted(loop):
-    from test_gpu_weighted_uca import circular_case
     o, dp = circular_case(loop)
     indptr, indices, _ = o.A
     src = np.repeat(np.arange(dp.shape[0] * dp.shape[1]), np.diff(indptr))
@@ -130,12 +100,7 @@ def test_circular_drainage_is_nan_and_counted(loop):
 
 
 def test_nan_specks():
-    from pydem_amd import synth
-    z = synth.fractal(640, 700, seed=7, top_shift=7, n_octaves=7)
-    rng = np.random.default_rng(3)
-    z[rng.integers(0, 640, 40), rng.integers(0, 700, 40)] = np.nan
-    z[0, 5] = np.nan; z[639, 300] = np.nan; z[200, 0] = np.nan
-    o, dp = pair(z, dX=30.0, dY=30.0)
+    z, o, dp, _ = nan_speck_pair((640, 700), 40, [(0, 5), (639, 300), (200, 0)])
     assert np.isnan(np.asarray(dp.uca)).any()
     for edge_nan in (False, True):
         for kind, stat in (('h', 'max'), ('v', 'ave')):
@@ -184,7 +149,6 @@ SCHEDULE_CASES = (('h', 'max', True), ('s', 'ave', False), ('v', 'min', True))
 def schedule_results():
     """what the three schedules must agree on, bit for bit: (sha256 of the result, levels, unresolved) per call"""
     import sys
-    from test_gpu_weighted_uca import circular_case
     out = []
     for name, dp in (('fractal', fractal_pair(*FRACTALS[0])[1]), ('deep ramp', deep_pair()[1]), ('two_loops', circular_case('two_loops')[1])):
         for kind, stat, edge_nan in SCHEDULE_CASES:
@@ -204,7 +168,6 @@ def test_schedules(env):
     """the queue alone, tile passes to the end, the default (the switches are read once per process: a fresh child each), held
     to this process's results, which the other tests hold to the reference: identical bits across the three"""
     import re
-    from test_gpu_weighted_uca import run_child
     here = schedule_results()
     assert here[-1][3] > 0 and here[0][3] == 0
     r = run_child("from test_gpu_dist_up import schedule_results\nprint('RESULTS', schedule_results())\nprint('CHILD-OK')",
@@ -231,15 +194,9 @@ def test_schedules(env):
                 assert visits > 0 and qlevels > 0 and qcells > 0                         # the deep ramp reaches the queue by default
 
 
-def _snapshot(dp):
-    from test_gpu_dist_down import _snapshot as snap
-    return snap(dp)
-
-
 def test_state_integrity():
     """the call writes nothing but its own state: fields, graph words, pit lists and timings are bit-equal around it; the
     downslope distance, whose planes it shares, gives the same bits before and after it"""
-    from test_gpu_dist_down import _same_snapshot
     from pydem_amd import DEMProcessor, synth
     z = synth.fractal(520, 700, seed=11, top_shift=7, n_octaves=7)
     with warnings.catch_warnings():

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import flow_fields as F
+from flowgraph_kit import _same_snapshot, _snapshot, assert_bound, bits, random_weights, run_child
 from test_dist_down_ref import KINDS, STATS, dist_down_ref
 from test_dist_up_ref import dist_up_ref
 from test_rev_accum_ref import rev_accum_ref
@@ -51,7 +52,6 @@ def processor(field):
 def pair(name):
     """(oracle after calc_uca, DEMProcessor after calc_uca) on the field `name`, with the precondition of every test here: the
     device's edge set is the oracle's.  The tile's snapshot right after calc_uca is kept for test_state_is_unchanged."""
-    from test_gpu_dist_down import _snapshot
     from test_gpu_parity import assert_edge_set_equals_oracle
     field = FIELDS[name]()
     o, dp = F.oracle(field), processor(field)
@@ -65,7 +65,6 @@ DEPTHS = {}             # (field, call) -> depth of the reference, filled by who
 
 
 def weights(name, seed=7):
-    from test_gpu_weighted_uca import random_weights
     return random_weights(FIELDS[name]().elev.shape, seed)
 
 
@@ -164,19 +163,19 @@ def test_closed_forms_on_the_chains(name):
 @pytest.mark.parametrize('k', range(8))
 def test_fans_agree_with_their_mirror_image(k):
     """a weight given to the wrong neighbour breaks this even if the reference shared the mistake"""
-    from test_gpu_rev_accum import assert_bound
     o, dp = pair('fan%d' % k)
     _, dpm = pair('fan%d_mirror' % k)
     refabs = rev_accum_ref(o, 0, seed=1.0)[0]
     a, _ = dp.calc_rev_accum(1.0)
     b, _ = dpm.calc_rev_accum(1.0)
     assert a.max() > 10 and np.isfinite(a).all()
-    assert_bound(a, b[:, ::-1], refabs, 'fan%d against its mirror image' % k)
+    bound, floor = 1e-9, 1e-300                  # (those of test_gpu_rev_accum's comparisons)
+    assert_bound(a, b[:, ::-1], refabs, 'fan%d against its mirror image' % k, bound, floor)
     # the same for a load that is not symmetric itself
     w = weights('fan%d' % k, 11)
     a, am = dp.calc_rev_accum(w)
     b, bm = dpm.calc_rev_accum(np.ascontiguousarray(w[:, ::-1]))
-    assert_bound(a, b[:, ::-1], rev_accum_ref(o, 0, seed=np.abs(w))[0], 'fan%d against its mirror image, random load' % k)
+    assert_bound(a, b[:, ::-1], rev_accum_ref(o, 0, seed=np.abs(w))[0], 'fan%d against its mirror image, random load' % k, bound, floor)
     assert np.array_equal(am, bm[:, ::-1])
 
 
@@ -202,7 +201,6 @@ def schedule_results(make=None, keep=()):
     """{(field, call): (sha256 of the result, levels, unresolved cells)} for every field; `keep`: fields whose arrays are
     returned too.  A child process makes its own processors (it needs no oracle)."""
     import sys
-    from test_gpu_dist_up import bits
     out, arrays = {}, {}
     for name in NAMES:
         dp = make(name) if make else processor(FIELDS[name]())
@@ -244,7 +242,6 @@ def test_far_pit_is_finished_by_the_default_schedule():
 def test_schedules(env):
     """the queue alone, tile passes to the end, two passes then the queue (the switches are read once per process: a fresh child
     each, one GPU process at a time): the bits of the default schedule, which the other tests hold to the references"""
-    from test_gpu_weighted_uca import run_child
     here, _ = default_schedule()
     r = run_child("from test_gpu_flow_fields import schedule_results\nprint('RESULTS', schedule_results())\nprint('CHILD-OK')",
                   env=dict(env, PYDEM_DIST_DEBUG='1'), timeout=300)
@@ -288,7 +285,6 @@ def test_schedules(env):
 @pytest.mark.parametrize('name', FAMILIES)
 def test_state_is_unchanged(name):
     """fields, graph words, pit lists and timings of the tile are those calc_uca left, after every call above"""
-    from test_gpu_dist_down import _same_snapshot, _snapshot
     _, dp = pair(name)
     before = SNAPSHOTS[name]
     assert len(before[0]) >= 6 and before[1].size == dp.shape[0] * dp.shape[1]

@@ -13,7 +13,6 @@ the smallest fractal tile of tests/test_gpu_dist_down.py with its pits drained (
 with several pits).  The default schedule only: test_gpu_flow_fields.test_schedules holds the other three to its bits.  That
 the values are RIGHT is the business of the cell-by-cell tests; this one only says they have not moved."""
 import functools
-import hashlib
 import json
 import os
 import sys
@@ -21,6 +20,8 @@ import warnings
 
 import numpy as np
 import pytest
+
+from flowgraph_kit import bits, random_weights
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, 'golden', 'flowgraph_bits.json')
@@ -30,14 +31,8 @@ NAMES = DESIGNED + (FRACTAL,)
 KINDS, STATS = ('h', 'v', 's'), ('ave', 'min', 'max')
 
 
-def bits(a):
-    a = np.ascontiguousarray(a, np.float64)
-    return hashlib.sha256(a.tobytes()).hexdigest()
-
-
 def processor_and_target(name):
     """(DEMProcessor after calc_uca, target mask of the downslope calls and the dependence, load of racc / dmax)"""
-    from test_gpu_weighted_uca import random_weights
     if name == FRACTAL:
         from pydem_amd import DEMProcessor, synth
         from test_gpu_dist_down import CELL, FRACTALS

@@ -12,12 +12,14 @@ import warnings
 import numpy as np
 import pytest
 
+from flowgraph_kit import (_same_snapshot, _snapshot, assert_bound, bits, circular_case, nan_speck_pair, pair, random_weights, run_child,
+                           shared_deep_pair as deep_pair, shared_fractal_pair as fractal_pair)
 from test_dist_up_ref import edge_nan_cells
 from test_fwd_accum_ref import fwd_accum_ref
 
 pytestmark = pytest.mark.gpu
 
-BOUND = 1e-9
+BOUND = 1e-9            # (no floor: where refabs is 0 the device must give the reference's value)
 REFS = {}               # key -> (reference, reference on absolute values): computed once, shared, never written to
 
 
@@ -30,20 +32,6 @@ def reference(o, load, mult, cap, edge_nan, key=None):
     return REFS[key]
 
 
-def held(dev, ref, refabs, what):
-    """NaN patterns identical and |dev - ref| <= BOUND * refabs; prints the worst ratio"""
-    dev, ref, refabs = (np.asarray(x, np.float64) for x in (dev, ref, refabs))
-    nan_ref = np.isnan(ref)
-    err = np.abs(dev[~nan_ref] - ref[~nan_ref])
-    scale = np.abs(refabs[~nan_ref])
-    with np.errstate(invalid='ignore', divide='ignore'):
-        worst = float(np.nanmax(np.r_[0.0, err / np.maximum(scale, 1e-300)]))
-    print("%s: %.1f %% finite, max %.4g, worst |dev - ref| / refabs %.3g"
-          % (what, 100 * (1 - nan_ref.mean()), np.nanmax(ref) if not nan_ref.all() else np.nan, worst))
-    assert np.array_equal(np.isnan(dev), nan_ref), "%s: NaN patterns differ (%d device, %d reference)" % (what, np.isnan(dev).sum(), nan_ref.sum())
-    assert (err <= BOUND * scale).all(), "%s: %d cells off, worst %.3g of the scale" % (what, (err > BOUND * scale).sum(), worst)
-
-
 def compare(dev_v, dev_i, o, load, mult, cap, edge_nan, what, key=None, min_finite=None):
     """the device's V (and I, and the deposition they give, when dev_i is not None) against the reference: (V, I, final, depth)"""
     (V, I, final, depth), (Va, Ia, _, _) = reference(o, load, mult, cap, edge_nan, key)
@@ -51,24 +39,13 @@ def compare(dev_v, dev_i, o, load, mult, cap, edge_nan, what, key=None, min_fini
     print("%s: depth %d, %d cells not final" % (what, depth, (~final).sum()))
     if min_finite is not None:
         assert finite >= min_finite, "%s: only %.1f %% of the reference is finite" % (what, 100 * finite)
-    held(dev_v, V, Va, what + ' V')
+    assert_bound(dev_v, V, Va, what + ' V', BOUND)
     if dev_i is not None:
-        held(dev_i, I, Ia, what + ' I')
+        assert_bound(dev_i, I, Ia, what + ' I', BOUND)
         ld = np.broadcast_to(np.asarray(load, np.float64), V.shape)
         with np.errstate(invalid='ignore'):
-            held((ld + dev_i) - dev_v, (ld + I) - V, Va, what + ' D')
+            assert_bound((ld + dev_i) - dev_v, (ld + I) - V, Va, what + ' D', BOUND)
     return V, I, final, depth
-
-
-def bits(a):
-    from test_gpu_dist_up import bits as sha
-    return sha(a)
-
-
-@functools.lru_cache(maxsize=None)
-def fractal_pair(shape, seed):
-    from test_gpu_weighted_uca import fractal_pair as make
-    return make(shape, seed)
 
 
 FRACTALS = [((300, 260), 5), ((700, 520), 41)]
@@ -76,7 +53,6 @@ FRACTALS = [((300, 260), 5), ((700, 520), 41)]
 
 def loads(shape, seed):
     """(signed load, mult in [0.5, 1], supply >= 0) of a tile"""
-    from test_gpu_weighted_uca import random_weights
     rng = np.random.default_rng(seed + 100)
     return random_weights(shape, seed), rng.uniform(0.5, 1.0, shape), rng.uniform(0.0, 2.0, shape)
 
@@ -148,7 +124,6 @@ def test_fractal_tiles_trans_lim(shape, seed, edge_nan):
 @pytest.mark.parametrize('shape', [(3, 7), (7, 3), (31, 33), (33, 65)])
 def test_small_ramps(shape):
     """tiles smaller than one 32 x 32 block, and one cell more than a block in each direction"""
-    from test_gpu_dist_up import pair
     n, m = shape
     z = -np.tile(np.arange(m, dtype=np.float64), (n, 1)) + 0.01 * np.arange(n, dtype=np.float64)[:, None]
     o, dp = pair(z, dX=2.0, dY=3.0)
@@ -169,14 +144,8 @@ def test_small_ramps(shape):
 
 # ---- 3. NaN specks
 def test_nan_specks():
-    from pydem_amd import synth
-    from test_gpu_dist_up import pair
     n, m = 200, 230
-    z = synth.fractal(n, m, seed=7, top_shift=7, n_octaves=7)
-    rng = np.random.default_rng(3)
-    z[rng.integers(0, n, 40), rng.integers(0, m, 40)] = np.nan
-    z[0, 5] = np.nan; z[n - 1, 100] = np.nan; z[60, 0] = np.nan
-    o, dp = pair(z, dX=30.0, dY=30.0)
+    z, o, dp, _ = nan_speck_pair((n, m), 40, [(0, 5), (n - 1, 100), (60, 0)])
     assert np.isnan(np.asarray(dp.uca)).any()
     w, k, s = loads((n, m), 3)
     for edge_nan in (False, True):
@@ -197,7 +166,6 @@ def test_nan_specks():
 # ---- 4. circular drainage
 @pytest.mark.parametrize('loop', ['two_cells', 'three_cells', 'two_loops'])
 def test_circular_drainage_is_nan_and_counted(loop):
-    from test_gpu_weighted_uca import circular_case
     o, dp = circular_case(loop)
     n, m = dp.shape
     indptr, indices, _ = o.A
@@ -222,12 +190,6 @@ def test_circular_drainage_is_nan_and_counted(loop):
 
 
 # ---- 5. deep ramp
-@functools.lru_cache(maxsize=None)
-def deep_pair():
-    from test_gpu_dist_down import deep_pair as make
-    return make()
-
-
 @functools.lru_cache(maxsize=None)
 def deep_ramp_depth():
     return fwd_accum_ref(deep_pair()[0], 1.0)[3]
@@ -321,7 +283,6 @@ def test_closed_forms_on_the_chains(name):
 def test_fans_agree_with_their_mirror_image(k):
     """a weight given to the wrong neighbour breaks this even if the reference shared the mistake"""
     from test_gpu_flow_fields import weights
-    from test_gpu_rev_accum import assert_bound
     o, dp = field_pair('fan%d' % k)
     _, dpm = field_pair('fan%d_mirror' % k)
     w = weights('fan%d' % k, 11)
@@ -332,20 +293,20 @@ def test_fans_agree_with_their_mirror_image(k):
     a = dp.calc_decay_accum(w, decay=mult, edge_nan=False)
     b = dpm.calc_decay_accum(wm, decay=multm, edge_nan=False)
     assert np.isfinite(a).all() and np.abs(a).max() > 2
-    assert_bound(a, b[:, ::-1], refabs, 'fan%d against its mirror image, decay' % k)
+    floor = 1e-300                     # (the mirror images are held with the floor of test_gpu_rev_accum's comparisons)
+    assert_bound(a, b[:, ::-1], refabs, 'fan%d against its mirror image, decay' % k, BOUND, floor)
     cap = field_cap(o, 'fan%d' % k)
     Ta, Da = dp.calc_trans_lim_accum(1.0, cap, edge_nan=False)
     Tb, Db = dpm.calc_trans_lim_accum(1.0, np.ascontiguousarray(cap[:, ::-1]), edge_nan=False)
     count = reference(o, 1.0, None, None, False, key=('fan%d' % k, 'count'))[0][0]
-    assert_bound(Ta, Tb[:, ::-1], count, 'fan%d against its mirror image, transport' % k)
-    assert_bound(Da, Db[:, ::-1], count, 'fan%d against its mirror image, deposition' % k)
+    assert_bound(Ta, Tb[:, ::-1], count, 'fan%d against its mirror image, transport' % k, BOUND, floor)
+    assert_bound(Da, Db[:, ::-1], count, 'fan%d against its mirror image, deposition' % k, BOUND, floor)
 
 
 # ---- 7. schedules
 def schedule_results():
     """what the three schedules must agree on, bit for bit: (case, sha256 of V, sha256 of I, levels, unresolved) per call"""
     import sys
-    from test_gpu_weighted_uca import circular_case
     out = []
     for name, dp in (('fractal', fractal_pair(*FRACTALS[0])[1]), ('deep ramp', deep_pair()[1]), ('two_loops', circular_case('two_loops')[1])):
         shape = tuple(dp.shape)
@@ -366,7 +327,6 @@ def test_schedules(env):
     """the queue alone, tile passes to the end, the default (the switches are read once per process: a fresh child each), held
     to this process's results, which the other tests hold to the reference: identical bits of V and I across the three"""
     import re
-    from test_gpu_weighted_uca import run_child
     here = schedule_results()
     assert here[-1][4] > 0 and here[0][4] == 0
     r = run_child("from test_gpu_fwd_accum import schedule_results\nprint('RESULTS', schedule_results())\nprint('CHILD-OK')",
@@ -400,7 +360,6 @@ def test_state_integrity():
     """the calls write nothing but their own state: fields, graph words, pit lists and timings are bit-equal around them; the
     three other sweeps, whose planes they share (the seed plane of the reverse accumulation included), give the same bits
     before and after; a repeated call gives the same bits"""
-    from test_gpu_dist_down import _same_snapshot, _snapshot
     from pydem_amd import DEMProcessor, synth
     shape = (260, 350)
     z = synth.fractal(shape[0], shape[1], seed=11, top_shift=7, n_octaves=7)

@@ -8,12 +8,13 @@ cell by cell:
 graph; the floor covers subnormal products; a max rounds nothing).  The tiles are the smallest that reach every path: (70, 45)
 is 3 x 2 blocks of 32 x 32, both ragged; (96, 80) 3 x 3; (160, 130) 5 x 5 with a 2-column sliver and some 600 pit edges.
 Then: the duality with the device's own uca, the schedules, what the call must leave alone, run-to-run identity, memory."""
-import functools
 import warnings
 
 import numpy as np
 import pytest
 
+from flowgraph_kit import (_same_snapshot, _snapshot, assert_bound, assert_same_bits, circular_case, deep_pair, fractal_pair as make,
+                           nan_speck_pair, random_weights, run_child, shared_fractal_pair as fractal_pair)
 from test_rev_accum_ref import OUTLETS, rev_accum_ref
 
 pytestmark = pytest.mark.gpu
@@ -24,57 +25,13 @@ CELL = 900.0            # dX * dY of the fractal tiles
 TILES = [(shape, seed) for shape, seed, _ in OUTLETS]
 
 
-def assert_same_bits(dev, ref, what):
-    dev, ref = np.asarray(dev, np.float64), np.asarray(ref, np.float64)
-    nd, nr = np.isnan(dev), np.isnan(ref)
-    assert np.array_equal(nd, nr), "%s: NaN patterns differ (%d device, %d reference)" % (what, nd.sum(), nr.sum())
-    bad = dev[~nd].view(np.int64) != ref[~nr].view(np.int64)
-    assert not bad.any(), "%s: %d cells differ in their bits" % (what, bad.sum())
-
-
-def assert_bound(dev, ref, refabs, what):
-    dev, ref, refabs = (np.asarray(x, np.float64) for x in (dev, ref, refabs))
-    nd, nr = np.isnan(dev), np.isnan(ref)
-    assert np.array_equal(nd, nr), "%s: NaN patterns differ (%d device, %d reference)" % (what, nd.sum(), nr.sum())
-    err = np.abs(dev[~nr] - ref[~nr])
-    lim = BOUND * np.abs(refabs[~nr]) + FLOOR
-    worst = float(np.max(np.r_[0.0, err / lim])) * BOUND
-    print("%s: %.1f %% NaN, worst |dev - ref| / refabs %.3g" % (what, 100 * nr.mean(), worst))
-    assert (err <= lim).all(), "%s: %d cells off, worst %.3g of the scale" % (what, (err > lim).sum(), worst)
-
-
 def compare(dev, o, op, what, seed=None, absorb=None, absorb_value=1.0):
     ref, final, depth = rev_accum_ref(o, op, seed, absorb, absorb_value)
     if op == 1:
         assert_same_bits(dev, ref, what)
     else:
-        assert_bound(dev, ref, rev_accum_ref(o, op, seed, absorb, absorb_value, absolute=True)[0], what)
+        assert_bound(dev, ref, rev_accum_ref(o, op, seed, absorb, absorb_value, absolute=True)[0], what, BOUND, FLOOR)
     return ref, final, depth
-
-
-@functools.lru_cache(maxsize=None)
-def fractal_pair(shape, seed):
-    from test_gpu_weighted_uca import fractal_pair as make
-    return make(shape, seed)
-
-
-def deep_pair_small():
-    """the ramp of test_gpu_dist_down.deep_pair at (200, 48)"""
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor
-    n, m = 200, 48
-    row, col = np.arange(n, dtype=np.float64)[:, None], np.arange(m, dtype=np.float64)[None, :]
-    z = 2000 - 1.5 * row + 10 * np.sin(col / 37) * row / n + np.random.default_rng(1).normal(0, 0.4, (n, m))
-    o = O.OracleDEM(z, dX=30.0, dY=30.0, drain_pits=True)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        dp.calc_uca()
-    target = np.zeros((n, m), bool)
-    target[-2:] = True
-    return o, dp, target
 
 
 # ---- 1. dependence on stream targets
@@ -126,7 +83,6 @@ def test_dependence_is_dual_to_the_devices_uca(shape, seed, outlet):
 # ---- 3. reverse accumulation of random loads
 @pytest.mark.parametrize('shape,seed', TILES)
 def test_rev_accum_random_weights(shape, seed):
-    from test_gpu_weighted_uca import random_weights
     o, dp = fractal_pair(shape, seed)
     w1, w2 = random_weights(shape, seed), random_weights(shape, seed + 1)
     r1, m1 = dp.calc_rev_accum(w1)
@@ -138,14 +94,16 @@ def test_rev_accum_random_weights(shape, seed):
     r2, _ = dp.calc_rev_accum(w2)
     r12, m12 = dp.calc_rev_accum(w1 + w2)
     compare(m12, o, 1, 'dmax of the sum %r' % (shape,), seed=w1 + w2)
-    assert_bound(r12, r1 + r2, rev_accum_ref(o, 0, seed=np.abs(w1) + np.abs(w2))[0], 'linearity %r' % (shape,))
+    assert_bound(r12, r1 + r2, rev_accum_ref(o, 0, seed=np.abs(w1) + np.abs(w2))[0], 'linearity %r' % (shape,), BOUND, FLOOR)
     r0, m0 = dp.calc_rev_accum(0.0)
     assert (r0 == 0.0).all() and (m0 == 0.0).all()
 
 
 # ---- 4. deep chain
 def check_deep():
-    o, dp, target = deep_pair_small()
+    o, dp = deep_pair((200, 48))
+    target = np.zeros(dp.shape, bool)
+    target[-2:] = True
     dep = dp.calc_up_dependence(target)
     _, final, depth = compare(dep, o, 0, 'deep ramp', absorb=target)
     st = dp.up_dependence_stats
@@ -163,7 +121,6 @@ def test_deep_chain():
 
 # ---- 5. circular drainage
 def check_circular(loop):
-    from test_gpu_weighted_uca import circular_case
     o, dp = circular_case(loop)
     n, m = dp.shape
     absorb = np.zeros((n, m), bool)
@@ -192,20 +149,9 @@ def test_circular_drainage_is_nan_and_counted(loop):
 
 # ---- 6. NaN specks
 def test_nan_specks():
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor, synth
     n, m = 96, 80
-    z = synth.fractal(n, m, seed=7, top_shift=7, n_octaves=7)
-    rng = np.random.default_rng(3)
-    z[rng.integers(0, n, 12), rng.integers(0, m, 12)] = np.nan
-    z[0, 5] = np.nan; z[95, 30] = np.nan; z[20, 0] = np.nan
-    o = O.OracleDEM(z, dX=30.0, dY=30.0, drain_pits=True)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        uca = np.array(dp.calc_uca())
+    z, o, dp, rng = nan_speck_pair((n, m), 12, [(0, 5), (95, 30), (20, 0)])
+    uca = np.array(dp.uca)
     nodata = np.isnan(z)
     assert 13 <= nodata.sum() <= 15
     target = uca >= 50 * CELL
@@ -240,7 +186,6 @@ def check_schedules():
 @pytest.mark.parametrize('env', [{'PYDEM_DIST_PASSES': '0'}, {'PYDEM_DIST_MIN_PER_VISIT': '0'}, {'PYDEM_DIST_PASSES': '2'}])
 def test_schedules(env):
     """the queue alone, tile passes to the end, two passes then the queue (the switches are read once per process)"""
-    from test_gpu_weighted_uca import run_child
     r = run_child("from test_gpu_rev_accum import check_schedules\nprint('LEVELS', check_schedules())\nprint('CHILD-OK')", env=env, timeout=300)
     (lv, lv_down, depth), (deep, deep_down, deep_depth) = eval(r.stdout.split('LEVELS', 1)[1].splitlines()[0])
     print(env, (lv, lv_down, depth), (deep, deep_down, deep_depth))
@@ -253,8 +198,7 @@ def test_schedules(env):
 
 # ---- 8. state integrity
 def test_state_integrity():
-    from test_gpu_dist_down import _snapshot, _same_snapshot, compare as compare_dist
-    from test_gpu_weighted_uca import assert_bitwise, fractal_pair as make, random_weights
+    from test_gpu_dist_down import compare as compare_dist
     shape, seed = TILES[0]
     o, dp = make(shape, seed)                           # (a pair of this test's own: it adds fields to the tile)
     n, m = shape
@@ -270,7 +214,7 @@ def test_state_integrity():
         racc, dmax = dp.calc_rev_accum(random_weights(shape, 3))
         assert np.isfinite(dep).any() and not np.array_equal(dep, racc, equal_nan=True) and not np.array_equal(racc, dmax, equal_nan=True)
         _same_snapshot(before, _snapshot(dp))
-        assert_bitwise(dp.calc_weighted_uca(1.0), uca, 'w = 1 after the reverse accumulation')
+        assert_same_bits(dp.calc_weighted_uca(1.0), uca, 'w = 1 after the reverse accumulation')
         # the calls share their planes: each still matches its reference after the other
         compare_dist(dp.calc_dist_down(target=target), o, target, 'h', 'ave', 'dist_down after up_dependence')
         compare(dp.calc_up_dependence(target), o, 0, 'up_dependence after dist_down', absorb=target)
@@ -283,7 +227,6 @@ def test_state_integrity():
 # ---- 9. repeatability and memory
 def test_identical_calls_and_no_growth():
     from pydem_amd import _ffi
-    from test_gpu_weighted_uca import random_weights
     shape, seed = TILES[1]
     o, dp = fractal_pair(shape, seed)
     target = np.asarray(dp.uca) >= 100 * CELL

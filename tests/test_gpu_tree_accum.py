@@ -14,6 +14,7 @@ import warnings
 import numpy as np
 import pytest
 
+from flowgraph_kit import _same_snapshot, _snapshot, circular_case, deep_pair, fractal_pair as make, nan_speck_pair, run_child
 from test_gpu_stream_network import TILES, device_edges, fractal_case, stream_set
 from test_stream_network_ref import stream_network_ref, top_fraction
 from test_tree_accum_ref import OPS, finite_below_nan, reach_table_ref, tree_accum_ref
@@ -260,8 +261,7 @@ def test_designed_fields(name):
 
 # ---- 5. the deep ramp, circular drainage, NaN specks
 def check_deep():
-    from test_gpu_rev_accum import deep_pair_small
-    o, dp, _ = deep_pair_small()
+    o, dp = deep_pair((200, 48))
     z = np.asarray(o.elev, np.float64)
     edges = device_edges(dp, z)
     every = np.ones(z.shape, bool)
@@ -283,7 +283,6 @@ def test_deep_chain():
 
 
 def check_circular(loop):
-    from test_gpu_weighted_uca import circular_case
     o, dp = circular_case(loop)
     z = np.asarray(o.elev, np.float64)
     edges = device_edges(dp, z)
@@ -309,17 +308,8 @@ def test_circular_drainage_is_nan_and_counted(loop):
 
 
 def test_nan_specks():
-    from pydem_amd import DEMProcessor, synth
     n, m = 96, 80
-    z = synth.fractal(n, m, seed=7, top_shift=7, n_octaves=7)
-    rng = np.random.default_rng(3)
-    z[rng.integers(0, n, 12), rng.integers(0, m, 12)] = np.nan
-    z[0, 5] = np.nan; z[95, 30] = np.nan; z[20, 0] = np.nan
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        dp.calc_uca()
+    z, _, dp, _ = nan_speck_pair((n, m), 12, [(0, 5), (95, 30), (20, 0)])
     nodata = np.isnan(z)
     edges = device_edges(dp, z)
     thr = 50 * 900.0
@@ -352,15 +342,12 @@ def check_schedules():
 @pytest.mark.parametrize('env', [{'PYDEM_DIST_PASSES': '0'}, {'PYDEM_DIST_MIN_PER_VISIT': '0'}, {'PYDEM_DIST_PASSES': '2'}])
 def test_schedules(env):
     """the queue alone, tile passes to the end, two passes then the queue (the switches are read once per process)"""
-    from test_gpu_weighted_uca import run_child
     r = run_child("from test_gpu_tree_accum import check_schedules\nprint('LEVELS', check_schedules())\nprint('CHILD-OK')", env=env, timeout=300)
     print(env, r.stdout.split('LEVELS', 1)[1].splitlines()[0])
 
 
 # ---- 7. state integrity
 def test_state_integrity():
-    from test_gpu_dist_down import _snapshot, _same_snapshot
-    from test_gpu_weighted_uca import fractal_pair as make
     shape, seed = TILES[1]
     o, dp = make(shape, seed)                           # (a pair of this test's own)
     with warnings.catch_warnings():

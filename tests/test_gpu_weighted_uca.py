@@ -5,19 +5,17 @@ must leave alone.
 The reference: the graph of OracleDEM.build_graph() (o.A), oracle.tocsr, oracle.drain_area started from w * dX2 * dY2 (or w)
 with edge-todo arrays passed so that sources are marked done like oracle_uca_chunk does (pydem_oracle.c:727-800), the re-seed
 loop of :951-964, NaN on flats.  With w = 1 it is o.uca exactly (test_reference_helper_pins_itself)."""
-import os
-import subprocess
-import sys
 import warnings
 
 import numpy as np
 import pytest
 
+from flowgraph_kit import (_strips, assert_bound, assert_same_bits, circular_case, fractal_pair, nan_speck_pair, random_weights,
+                           run_child)
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BOUND = 1e-9        # |dev - ref| <= BOUND * ref(|w|), cell by cell
+BOUND = 1e-9        # |dev - ref| <= BOUND * ref(|w|), cell by cell, no floor (ref(|w|) >= 0: a sweep of non-negative seeds)
 
 
 def weighted_ref(o, w, scale_by_cell_area=True):
@@ -56,83 +54,31 @@ def weighted_ref(o, w, scale_by_cell_area=True):
     return area
 
 
-def assert_bitwise(a, b, what):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    assert np.array_equal(na, nb), "%s: NaN patterns differ (%d vs %d)" % (what, na.sum(), nb.sum())
-    bad = a[~na].view(np.int64) != b[~nb].view(np.int64)
-    assert not bad.any(), "%s: %d cells differ in their bits" % (what, bad.sum())
-
-
-def assert_bound(dev, ref, ref_abs, what):
-    dev, ref, ref_abs = (np.asarray(x, np.float64) for x in (dev, ref, ref_abs))
-    assert np.array_equal(np.isnan(dev), np.isnan(ref)), "%s: NaN patterns differ" % what
-    ok = ~np.isnan(ref)
-    err = np.abs(dev[ok] - ref[ok])
-    lim = BOUND * ref_abs[ok]
-    assert (err <= lim).all(), "%s: %d cells off, worst %.3g (bound %.3g)" % (what, (err > lim).sum(), err.max(), lim[np.argmax(err - lim)])
-
-
-def fractal_pair(shape, seed):
-    """(oracle after calc_uca, device processor after calc_uca) on a synthetic tile, drain_pits=True"""
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor, synth
-    z = synth.fractal(shape[0], shape[1], seed=seed, top_shift=7, n_octaves=7)
-    o = O.OracleDEM(z, dX=30.0, dY=30.0, drain_pits=True)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        dp.calc_uca()
-    return o, dp
-
-
-def random_weights(shape, seed):
-    rng = np.random.default_rng(seed)
-    w = rng.uniform(-1.0, 2.0, shape)
-    w[rng.random(shape) < 0.15] = 0.0                                # >= 10 % exact zeros
-    assert (w == 0).mean() >= 0.10
-    return w
-
-
 def check_tile(o, dp, seed=0):
     """The identities with uca and the comparisons with the reference on one tile (shared with the child processes)."""
     n, m = dp.shape
     uca = np.array(dp.uca)
-    assert_bitwise(dp.calc_weighted_uca(1.0), uca, 'w = 1')
-    assert_bitwise(dp.calc_weighted_uca(np.full((n, m), 0.25)), 0.25 * uca, 'w = 0.25')
+    assert_same_bits(dp.calc_weighted_uca(1.0), uca, 'w = 1')
+    assert_same_bits(dp.calc_weighted_uca(np.full((n, m), 0.25)), 0.25 * uca, 'w = 0.25')
     a0 = np.broadcast_to((dp.dX2 * dp.dY2)[:, None], (n, m))
-    assert_bitwise(dp.calc_weighted_uca(a0, scale_by_cell_area=False), uca, 'w = dX2 * dY2, unscaled')
+    assert_same_bits(dp.calc_weighted_uca(a0, scale_by_cell_area=False), uca, 'w = dX2 * dY2, unscaled')
     w1, w2 = random_weights((n, m), seed), random_weights((n, m), seed + 1)
     ref_abs = weighted_ref(o, np.abs(w1))
     d1 = np.array(dp.calc_weighted_uca(w1))
-    assert_bound(d1, weighted_ref(o, w1), ref_abs, 'random weights')
+    assert_bound(d1, weighted_ref(o, w1), ref_abs, 'random weights', BOUND)
     cnt = np.array(dp.calc_weighted_uca(1.0, scale_by_cell_area=False))
-    assert_bound(cnt, weighted_ref(o, 1.0, scale_by_cell_area=False), weighted_ref(o, 1.0, scale_by_cell_area=False), 'cell counts')
+    assert_bound(cnt, weighted_ref(o, 1.0, scale_by_cell_area=False), weighted_ref(o, 1.0, scale_by_cell_area=False), 'cell counts', BOUND)
     d2 = np.array(dp.calc_weighted_uca(w2))
     d12 = np.array(dp.calc_weighted_uca(w1 + w2))
-    assert_bound(d12, d1 + d2, weighted_ref(o, np.abs(w1) + np.abs(w2)), 'linearity')
+    assert_bound(d12, d1 + d2, weighted_ref(o, np.abs(w1) + np.abs(w2)), 'linearity', BOUND)
     # the plain result is untouched by all of this
-    assert_bitwise(dp.uca, uca, 'uca after the weighted calls')
+    assert_same_bits(dp.uca, uca, 'uca after the weighted calls')
     return dp.timings
-
-
-def run_child(body, env=None, timeout=600):
-    """A python child with the GPU open (one at a time): `body` runs after the imports of this module's helpers."""
-    script = "\n".join(["import sys, warnings", "sys.path.insert(0, %r); sys.path.insert(0, %r)" % (ROOT, HERE),
-                        "warnings.simplefilter('ignore')", "import numpy as np",
-                        "from test_gpu_weighted_uca import *", body])
-    e = dict(os.environ)
-    e.update(env or {})
-    r = subprocess.run([sys.executable, '-c', script], env=e, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
-    assert r.returncode == 0 and 'CHILD-OK' in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
 
 
 def test_reference_helper_pins_itself():
     o, _ = fractal_pair((300, 260), 5)
-    assert_bitwise(weighted_ref(o, 1.0), o.uca, 'helper with w = 1')
+    assert_same_bits(weighted_ref(o, 1.0), o.uca, 'helper with w = 1')
 
 
 @pytest.mark.parametrize('shape,seed', [((700, 520), 41), ((1024, 1024), 42)])
@@ -143,48 +89,13 @@ def test_weighted_fractal_tiles(shape, seed):
 
 
 def test_nan_specks_identity():
-    from pydem_amd import DEMProcessor, synth
-    z = synth.fractal(640, 700, seed=7, top_shift=7, n_octaves=7)
-    rng = np.random.default_rng(3)
-    z[rng.integers(0, 640, 40), rng.integers(0, 700, 40)] = np.nan
-    z[0, 5] = np.nan; z[639, 300] = np.nan; z[200, 0] = np.nan
+    _, _, dp, _ = nan_speck_pair((640, 700), 40, [(0, 5), (639, 300), (200, 0)])
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        dp = DEMProcessor(elev=z, dX=30.0, dY=30.0, fill_flats=False, drain_pits_path=False, drain_pits=True)
-        dp.calc_slopes_directions()
-        uca = np.array(dp.calc_uca())
+        uca = np.array(dp.uca)
         assert np.isnan(uca).any()
-        assert_bitwise(dp.calc_weighted_uca(1.0), uca, 'w = 1 with NaN specks')
-        assert_bitwise(dp.calc_weighted_uca(2.0 ** -5), 2.0 ** -5 * uca, 'w = 2^-5 with NaN specks')
-
-
-def circular_case(loop):
-    """The hand-made loop fields of test_gpu_parity.py (oracle after calc_uca, device processor after calc_uca)."""
-    from oracle import oracle as O
-    from pydem_amd import DEMProcessor
-    n, m = 9, 10
-    elev = np.full((n, m), 10.0)
-    direction = np.full((n, m), 1.5 * np.pi)
-    E, N, W, S = 0.0, 0.5 * np.pi, np.pi, 1.5 * np.pi
-    if loop == 'two_cells':
-        direction[3, 3] = E; direction[3, 4] = W
-    elif loop == 'three_cells':
-        direction[3, 3] = E; direction[3, 4] = S; direction[4, 4] = 0.75 * np.pi
-    else:
-        direction[2, 2] = E; direction[2, 3] = W
-        direction[5, 6] = S; direction[6, 6] = N
-    mag = np.ones((n, m))
-    flats = np.zeros((n, m), bool)
-    o = O.OracleDEM(elev, dX=2.0, dY=3.0)
-    o.mag, o.direction, o.flats = mag.copy(), direction.copy(), flats.astype(np.uint8)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        o.calc_uca()
-        dp = DEMProcessor(elev=elev, dX=2.0, dY=3.0, mag=mag.copy(), direction=direction.copy(), flats=flats.copy(),
-                          fill_flats=False, drain_pits_path=False)
-        dp.calc_uca()
-    assert o.stats[0] > 1, "the case is meant to need the re-seed loop"
-    return o, dp
+        assert_same_bits(dp.calc_weighted_uca(1.0), uca, 'w = 1 with NaN specks')
+        assert_same_bits(dp.calc_weighted_uca(2.0 ** -5), 2.0 ** -5 * uca, 'w = 2^-5 with NaN specks')
 
 
 def check_circular():
@@ -195,10 +106,10 @@ def check_circular():
         w[::3, ::2] = 0.0
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
-            assert_bitwise(dp.calc_weighted_uca(1.0), dp.uca, loop + ': w = 1')
-            assert_bound(dp.calc_weighted_uca(w), weighted_ref(o, w), weighted_ref(o, np.abs(w)), loop + ': mixed weights')
+            assert_same_bits(dp.calc_weighted_uca(1.0), dp.uca, loop + ': w = 1')
+            assert_bound(dp.calc_weighted_uca(w), weighted_ref(o, w), weighted_ref(o, np.abs(w)), loop + ': mixed weights', BOUND)
             assert_bound(dp.calc_weighted_uca(w, scale_by_cell_area=False), weighted_ref(o, w, False),
-                         weighted_ref(o, np.abs(w), False), loop + ': mixed weights, unscaled')
+                         weighted_ref(o, np.abs(w), False), loop + ': mixed weights, unscaled', BOUND)
 
 
 def test_circular_drainage_mixed_weights():
@@ -207,14 +118,14 @@ def test_circular_drainage_mixed_weights():
 
 def test_circular_drainage_host_replay():
     """the same with the re-seed replay on the host (PYDEM_RESEED_HOST_ABOVE=0; the switch is read once per process)"""
-    r = run_child("check_circular()\nprint('CHILD-OK')", env={'PYDEM_RESEED_HOST_ABOVE': '0'})
+    r = run_child("from test_gpu_weighted_uca import check_circular\ncheck_circular()\nprint('CHILD-OK')", env={'PYDEM_RESEED_HOST_ABOVE': '0'})
     assert 'the re-seed loop runs on the host' in r.stderr
 
 
 @pytest.mark.parametrize('env', [{'PYDEM_SWEEP_SYM': '0'}, {'PYDEM_SWEEP_SYM': '100000000'}, {'PYDEM_SWEEP_SYM': '40'},
                                  {'PYDEM_SWEEP_RESIDENT': '0'}, {'PYDEM_SWEEP_RESIDENT': '100000000'}])
 def test_weighted_schedules(env):
-    run_child("o, dp = fractal_pair((1024, 1024), 42)\ncheck_tile(o, dp, 42)\nprint('CHILD-OK')", env=env)
+    run_child("from test_gpu_weighted_uca import check_tile\no, dp = fractal_pair((1024, 1024), 42)\ncheck_tile(o, dp, 42)\nprint('CHILD-OK')", env=env)
 
 
 def test_weighted_bench_tile_8192():
@@ -225,23 +136,14 @@ dp = DEMProcessor.from_synthetic((8192, 8192), dict(seed=1), dX=30.0, dY=30.0, f
 dp.run_slopes_directions(); dp.run_uca()
 uca = np.array(dp.uca)
 sys.stderr.write('--- weighted calls\\n')
-assert_bitwise(dp.calc_weighted_uca(1.0), uca, 'w = 1 at 8192^2')
-assert_bitwise(dp.calc_weighted_uca(2.0 ** -3), 2.0 ** -3 * uca, 'w = 2^-3 at 8192^2')
-assert_bitwise(dp.uca, uca, 'uca after the weighted calls')
+assert_same_bits(dp.calc_weighted_uca(1.0), uca, 'w = 1 at 8192^2')
+assert_same_bits(dp.calc_weighted_uca(2.0 ** -3), 2.0 ** -3 * uca, 'w = 2^-3 at 8192^2')
+assert_same_bits(dp.uca, uca, 'uca after the weighted calls')
 print('CHILD-OK', dp.timings['sweep_ms'], dp.timings['uca_weighted_ms'])
 """
     r = run_child(body, env={'PYDEM_SWEEP_DEBUG': '1'}, timeout=900)
     weighted = r.stderr.split('--- weighted calls', 1)[1]
     assert weighted.count('symbolic pass') >= 2 and 'two-level solve' in weighted, r.stderr[-3000:]
-
-
-def _strips(n, m, seed):
-    rng = np.random.default_rng(seed)
-    lens = dict(left=n, right=n, top=m, bottom=m)
-    data = {k: rng.uniform(0, 5000, v) for k, v in lens.items()}
-    done = {k: rng.random(v) < 0.5 for k, v in lens.items()}
-    todo = {k: rng.random(v) < 0.3 for k, v in lens.items()}
-    return [data, done, todo]
 
 
 def _fields(dp):
@@ -295,9 +197,9 @@ def test_state_integrity():
         second = np.array(dp.calc_weighted_uca(w2))
         fresh = DEMProcessor(elev=z, **kw)
         fresh.run_slopes_directions()
-        assert_bitwise(second, fresh.calc_weighted_uca(w2), 'second weighted call')
+        assert_same_bits(second, fresh.calc_weighted_uca(w2), 'second weighted call')
         fresh.run_uca()
-        assert_bitwise(first, fresh.calc_weighted_uca(w), 'weighted call before / after calc_uca')
+        assert_same_bits(first, fresh.calc_weighted_uca(w), 'weighted call before / after calc_uca')
 
 
 def test_repeated_calls_without_calc_uca():
@@ -319,15 +221,15 @@ def test_repeated_calls_without_calc_uca():
         assert np.array_equal(np.array(dp.mag), mag0) and np.array_equal(np.array(dp.flats), flats0)
         tm1 = dp.timings
         assert all(tm1[k] == tm0[k] for k in tm0 if k != 'uca_weighted_ms')
-        assert_bitwise(dp.calc_weighted_uca(w), first, 'second call, same weights')
+        assert_same_bits(dp.calc_weighted_uca(w), first, 'second call, same weights')
         second = np.array(dp.calc_weighted_uca(w2))
-        assert_bitwise(dp.calc_weighted_uca(w), first, 'third call, the first weights again')
+        assert_same_bits(dp.calc_weighted_uca(w), first, 'third call, the first weights again')
         uca = np.array(dp.calc_uca())
         ref = DEMProcessor(elev=z, **kw)
         ref.run_slopes_directions()
-        assert_bitwise(uca, ref.calc_uca(), 'calc_uca after the weighted calls')
-        assert_bitwise(dp.calc_weighted_uca(1.0), uca, 'w = 1 after calc_uca')
-        assert_bitwise(dp.calc_weighted_uca(w2), second, 'the graph calc_uca built = the one the weighted call built')
+        assert_same_bits(uca, ref.calc_uca(), 'calc_uca after the weighted calls')
+        assert_same_bits(dp.calc_weighted_uca(1.0), uca, 'w = 1 after calc_uca')
+        assert_same_bits(dp.calc_weighted_uca(w2), second, 'the graph calc_uca built = the one the weighted call built')
 
 
 def test_changed_graph_options_rebuild_the_graph():
@@ -357,5 +259,5 @@ def test_changed_graph_options_rebuild_the_graph():
                 runs.append(got)
             else:
                 runs.append(np.array(dp.calc_uca()))         # calc_uca with the current options on the same tile
-        assert_bitwise(runs[0], runs[1], 'weighted w = 1 vs calc_uca with the changed options')
+        assert_same_bits(runs[0], runs[1], 'weighted w = 1 vs calc_uca with the changed options')
         assert not np.array_equal(runs[1], np.array(before['uca']), equal_nan=True), "the option change is meant to matter"
