@@ -114,11 +114,7 @@ int pydem_comm_destroy(pydem_comm *c)
 int pydem_comm_begin(pydem_comm *c, int64_t n_doubles)
 {
     HIP_TRY(hipSetDevice(c->device));
-    if ((size_t)n_doubles > c->cap) {
-        if (c->buf) HIP_TRY(hipFree(c->buf));
-        HIP_TRY(dev_malloc((void **)&c->buf, (size_t)n_doubles * 8));
-        c->cap = (size_t)n_doubles;
-    }
+    PYDEM_TRY(dev_reserve(&c->buf, &c->cap, (size_t)n_doubles, (size_t)n_doubles));
     HIP_TRY(hipMemsetAsync(c->buf, 0, (size_t)n_doubles * 8, c->stream));
     HIP_TRY(hipEventRecord(c->ev_clear, c->stream));      // the packs wait for this on their own streams
     return 0;
@@ -698,7 +694,8 @@ int pydem_board_set_lines(pydem_board *b, int index, int64_t mb_start, int64_t s
         P.rel = rel_offsets[k]; P.bytes = (int32_t)elem;
         if (P.rel < 0 || P.rel + P.count > size) { pydem_set_error("pydem_board_set_lines: line beyond the tile's board segment"); return -2; }
     }
-    if (T.lines) HIP_TRY(hipFree(T.lines));
+    dev_free(T.lines);
+    T.lines = nullptr;
     HIP_TRY(hipMalloc((void **)&T.lines, (size_t)(count > 0 ? count : 1) * sizeof(pydem_pack_line)));
     HIP_TRY(hipMemcpyAsync(T.lines, h.data(), (size_t)count * sizeof(pydem_pack_line), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -724,11 +721,7 @@ static int board_stage(pydem_board *b, int n_wave, const int *wave_tiles, bool s
         S.src[k] = total; S.dst[k] = b->tl[(size_t)i].mb_start; S.cnt[k] = b->tl[(size_t)i].size;
         total += b->tl[(size_t)i].size;
     }
-    if (total > b->wcap) {
-        if (b->wb) HIP_TRY(hipFree(b->wb));
-        HIP_TRY(dev_malloc((void **)&b->wb, (size_t)total * 8));
-        b->wcap = total;
-    }
+    PYDEM_TRY(dev_reserve(&b->wb, &b->wcap, (size_t)total, (size_t)total));
     if (summed) HIP_TRY(hipMemsetAsync(b->wb, 0, (size_t)total * 8, b->stream));
     HIP_TRY(hipEventRecord(b->ev, b->stream));
     for (int k = 0; k < n_wave; k++) {
@@ -854,10 +847,8 @@ static int board_prepare(pydem_board *b, bool staged, unsigned long long ok)
         b->h_progress[0] = b->h_progress[1] = 0;
     }
     if (b->cap > b->wcap) {
-        if (b->wb) HIP_TRY(hipFree(b->wb));
-        HIP_TRY(dev_malloc((void **)&b->wb, (size_t)b->cap * 8));
-        b->wcap = b->cap;
         board_drop_graphs(b); b->tables_valid = false;   // (they hold the old staging buffer)
+        PYDEM_TRY(dev_reserve(&b->wb, &b->wcap, (size_t)b->cap, (size_t)b->cap));
     }
     int64_t most = 1;
     std::vector<int> mine;

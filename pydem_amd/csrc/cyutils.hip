@@ -114,13 +114,6 @@ __global__ void k_cy_flood(const int32_t *__restrict__ front, int32_t nf, int32_
     }
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { if (bytes == 0) bytes = 8; HIP_TRY(hipMalloc(&p, bytes)); return 0; }
-    template <typename T> T *as() { return (T *)p; }
-};
-
 int front_from_mask(const uint8_t *mask, int64_t n, std::vector<int32_t> &out)
 {
     out.clear();
@@ -140,7 +133,7 @@ int pydem_drain_area(double *area, uint8_t *done, uint8_t *ids, const int32_t *c
     const int64_t N = n_rows * n_cols;
     if (N >= INT32_MAX) { pydem_set_error("graph too large for int32 ids"); return -2; }
     const int64_t nnz = col_indptr[N];
-    DevBuf d_area, d_done, d_cp, d_ci, d_cd, d_rp, d_ri, d_et, d_etn, d_mark, d_q0, d_q1, d_cnt, d_tmark, d_targets;
+    DevTemp d_area, d_done, d_cp, d_ci, d_cd, d_rp, d_ri, d_et, d_etn, d_mark, d_q0, d_q1, d_cnt, d_tmark, d_targets;
     PYDEM_TRY(d_area.alloc(N * 8)); PYDEM_TRY(d_done.alloc(N)); PYDEM_TRY(d_cp.alloc((N + 1) * 4)); PYDEM_TRY(d_ci.alloc(nnz * 4));
     PYDEM_TRY(d_cd.alloc(nnz * 8)); PYDEM_TRY(d_rp.alloc((N + 1) * 4)); PYDEM_TRY(d_ri.alloc(nnz * 4));
     PYDEM_TRY(d_mark.alloc(N * 4)); PYDEM_TRY(d_q0.alloc(N * 4)); PYDEM_TRY(d_q1.alloc(N * 4)); PYDEM_TRY(d_cnt.alloc(16));
@@ -215,7 +208,7 @@ int pydem_drain_connections(uint8_t *arr, uint8_t *ids, const int32_t *indptr, c
     HIP_TRY(hipSetDevice(device));
     if (n >= INT32_MAX) { pydem_set_error("graph too large for int32 ids"); return -2; }
     const int64_t nnz = indptr[n];
-    DevBuf d_arr, d_p, d_i, d_mark, d_q0, d_q1, d_cnt;
+    DevTemp d_arr, d_p, d_i, d_mark, d_q0, d_q1, d_cnt;
     PYDEM_TRY(d_arr.alloc(n * 4)); PYDEM_TRY(d_p.alloc((n + 1) * 4)); PYDEM_TRY(d_i.alloc(nnz * 4)); PYDEM_TRY(d_mark.alloc(n * 4));
     PYDEM_TRY(d_q0.alloc(n * 4)); PYDEM_TRY(d_q1.alloc(n * 4)); PYDEM_TRY(d_cnt.alloc(16));
     std::vector<int32_t> a32((size_t)n);

@@ -53,6 +53,9 @@ struct PitGraph {
     void *sort_buf = nullptr; size_t sort_bytes = 0;                        // keys / indices / radix-sort scratch, kept across calls
 };
 
+// one device block of a tile (tile_mem.h): the member that points to it, its size, and whether it came through the plane cache
+struct TileBlock { void **slot; size_t bytes; bool cached; };
+
 struct pydem_tile {
     int64_t n = 0, m = 0, NN = 0;
     int device = 0;
@@ -91,7 +94,7 @@ struct pydem_tile {
     int32_t *eseed = nullptr;       // seed frontier of the current edge round (cell, graph word) pairs
     bool edge_clean = false;        // edge flags / counts are zero and the masks only differ from their defaults on etodo_prev cells
     bool einc_compact = false;      // ... in the compact record form (one 128-byte record per not-done cell)
-    void *nd_rec = nullptr; int64_t nd_cap = 0; int32_t nd = 0;
+    void *nd_rec = nullptr; size_t nd_bytes = 0; int32_t nd = 0;
     int64_t circular_cells = -1;    // cells the last sweep found on / below a drainage loop (-1: no sweep ran on this handle)
     int64_t einc_round = 0;         // incremental edge rounds run on this tile so far (stamps of the NaN flood)
     bool einc_ready = false;        // incremental edge rounds: counts / deltas / FINAL flags are live (uca_edge.hip K7i)
@@ -109,7 +112,7 @@ struct pydem_tile {
     void *h_stage = nullptr; size_t h_stage_bytes = 0;      // pinned host staging of the conditioning stages (tile_pinned)
     int32_t etodo_prev = 0;         // cells whose edge_done byte the previous round cleared (tlist = flatlist)
     double *line_stage = nullptr;   // max(n, m) doubles: staging for column get/set
-    void *lines_stage = nullptr; int lines_cap = 0;   // staging for pydem_tile_get_lines
+    void *lines_stage = nullptr; size_t lines_bytes = 0;   // staging for pydem_tile_get_lines
     bool graph_valid = false;   // graph words/section/prop/pit lists match the resident elev/dir/flats
     // What is known about the resident flats mask against the resident slopes (tile.hip: pydem_find_flats only does the work its
     // result needs).  0: nothing.  1: flats[c] == (mag[c] == -1) for every cell.  2: as 1, except at the cells pits.raw_src[e] >= 0,
@@ -138,12 +141,10 @@ struct pydem_tile {
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;
     std::vector<pydem_depression> depr;     // the table of the last pydem_depressions (host memory; pydem_depressions_table copies it out)
+    std::vector<TileBlock> blocks;  // every device block the members above point to; device_bytes is their sum (both written by tile_mem.h only)
     int64_t device_bytes = 0;
     pydem_timings tm = {};
 };
-
-template <typename T>
-int tile_alloc(pydem_tile *t, T **p, size_t count);
 
 // Scratch of the conditioning stages (region records of pydem_fill_flats, reservation planes / footprints / trails of
 // pydem_pit_paths: 6 GB + up to 17 GB for the large-window simulations of a 8192^2 tile).  Allocating and freeing that
@@ -162,13 +163,22 @@ int arena_acquire(int device, ArenaLease *L);
 void *arena_take(ArenaLease *L, size_t bytes);       // 256-byte aligned; nullptr on allocation failure (error set)
 
 int ensure_fields(pydem_tile *t, std::initializer_list<int> fields);
-// pinned host memory of at least `bytes` that lives with the tile (grown on demand): every per-round transfer of the
-// conditioning stages goes through it -- asynchronous copies from / to pageable memory make the runtime pin and unpin
-// the pages behind the caller's back, and the NEXT GPU call then waits ~20 ms for that housekeeping
-// device blocks through the per-device free lists of tile.hip (planes of destroyed tiles are reused)
+// ---- device and pinned memory (devmem.hip)
+// device blocks through the per-device free lists (planes of destroyed tiles are reused)
 void *plane_take(int device, size_t bytes);
 void plane_give(int device, void *q);
 hipError_t dev_malloc(void **p, size_t bytes);      // hipMalloc; on failure the free lists are emptied and the call repeated
+void dev_free(void *p);                             // hipFree (a null pointer is fine)
+void devmem_release_all();                          // the arenas, the free lists and the transfer pools of every device (pydem_hip_release_scratch)
+struct DevTemp {                        // a temporary device block that is freed on every way out
+    void *p = nullptr;
+    ~DevTemp() { dev_free(p); }
+    int alloc(size_t bytes) { if (bytes == 0) bytes = 8; HIP_TRY(dev_malloc(&p, bytes)); return 0; }
+    template <typename T> T *as() { return (T *)p; }
+};
+// pinned host memory of at least `bytes` that lives with the tile (grown on demand): every per-round transfer of the
+// conditioning stages goes through it -- asynchronous copies from / to pageable memory make the runtime pin and unpin
+// the pages behind the caller's back, and the NEXT GPU call then waits ~20 ms for that housekeeping
 int tile_pinned(pydem_tile *t, size_t bytes, void **out);
 // whole-plane transfer between a device plane and a pageable host array (the tile's stream is drained first)
 int tile_plane_copy(pydem_tile *t, void *dev, void *host, size_t bytes, bool to_host);
@@ -225,3 +235,5 @@ static inline bool step_lean()
     const char *e = getenv("PYDEM_STEP_LEAN");
     return !(e && *e && atoi(e) == 0);
 }
+
+#include "tile_mem.h"       // tile_alloc / tile_reserve / tile_release_all: what a tile holds on the device

@@ -1354,11 +1354,14 @@ __global__ void k_pit_gather(const uint64_t *__restrict__ keys, const int32_t *_
     }
 }
 
+// one plane of a pit view grows to `count` entries.  A view's planes share one capacity in entries, which the caller has found
+// too small (and zeroes before the first plane goes back, sets once the last has grown): whatever this plane holds is replaced,
+// through the plane cache
 template <typename T>
-int dev_realloc(pydem_tile *t, T **p, size_t count)
+int view_grow(pydem_tile *t, T **p, size_t count)
 {
-    if (*p) { plane_give(t->device, *p); *p = nullptr; }      // (back to the device's free list: tile.hip)
-    return tile_alloc(t, p, count);
+    size_t held = 0;
+    return tile_reserve(t, p, &held, count * sizeof(T), count * sizeof(T), true);
 }
 
 }  // namespace
@@ -1393,17 +1396,19 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
     int64_t cap = (int64_t)npits * 2 + 16384 * 4 * OUT_CHUNK + 1024;   // + one partly used chunk per wavefront
     for (int attempt = 0;; attempt++) {
         if (t->pits.raw_cap < cap) {
-            PYDEM_TRY(dev_realloc(t, &t->pits.raw_src, (size_t)cap));
-            PYDEM_TRY(dev_realloc(t, &t->pits.raw_dst, (size_t)cap));
-            PYDEM_TRY(dev_realloc(t, &t->pits.raw_w, (size_t)cap));
+            t->pits.raw_cap = 0;
+            PYDEM_TRY(view_grow(t, &t->pits.raw_src, (size_t)cap));
+            PYDEM_TRY(view_grow(t, &t->pits.raw_dst, (size_t)cap));
+            PYDEM_TRY(view_grow(t, &t->pits.raw_w, (size_t)cap));
             t->pits.raw_cap = cap;
         }
         HIP_TRY(hipMemsetAsync(cnt + 1, 0, 8 * sizeof(int32_t), t->stream));
         PitParams P;
         P.dbg = nullptr; P.prof = nullptr;
         const char *dbg_env = getenv("PYDEM_PITS_DEBUG");
-        if (dbg_env && atoi(dbg_env) == 3) { HIP_TRY(hipMalloc(&P.prof, 128)); HIP_TRY(hipMemsetAsync(P.prof, 0, 128, t->stream)); }
-        if (dbg_env && atoi(dbg_env) >= 2) HIP_TRY(hipMalloc(&P.dbg, (size_t)npits * 16));
+        DevTemp d_prof, d_dbg;                              // (PYDEM_PITS_DEBUG: diagnostic blocks of this attempt)
+        if (dbg_env && atoi(dbg_env) == 3) { PYDEM_TRY(d_prof.alloc(128)); P.prof = d_prof.as<unsigned long long>(); HIP_TRY(hipMemsetAsync(P.prof, 0, 128, t->stream)); }
+        if (dbg_env && atoi(dbg_env) >= 2) { PYDEM_TRY(d_dbg.alloc((size_t)npits * 16)); P.dbg = d_dbg.as<int32_t>(); }
         HIP_TRY(hipMemsetAsync(t->pits.raw_src, 0xFF, (size_t)t->pits.raw_cap * 4, t->stream));   // -1 = unused slot
         P.elev = t->elev; P.pitmask = t->flat0; P.dX = t->dX; P.dY = t->dY; P.mag = t->mag; P.flats = t->flats;
         P.n = n; P.m = m; P.max_iter = opt->drain_pits_max_iter; P.max_dist = opt->drain_pits_max_dist;
@@ -1497,7 +1502,6 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
                 n_over = t->h_counters[9];
             }
         }
-        if (P.prof) { (void)hipFree(P.prof); P.prof = nullptr; }
         t->tm.n_pits_row = n_row_over >= 0 ? n_lane_over : 0;
         t->tm.n_pits_wave = n_row_over >= 0 ? n_row_over : n_lane_over;
         t->tm.n_pits_big = n_wave_over;
@@ -1506,7 +1510,6 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
             const int nrec = t->h_counters[7];
             std::vector<int32_t> rec((size_t)nrec * 4);
             HIP_TRY(hipMemcpy(rec.data(), P.dbg, rec.size() * 4, hipMemcpyDeviceToHost));
-            (void)hipFree(P.dbg); P.dbg = nullptr;
             std::vector<int> rounds, border; int reason[4] = {0, 0, 0, 0}; long long tot_rounds = 0;
             for (int i = 0; i < nrec; i++) {
                 rounds.push_back(rec[4 * i]); border.push_back(rec[4 * i + 1]); reason[rec[4 * i + 2] & 3]++; tot_rounds += rec[4 * i];
@@ -1541,11 +1544,7 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
             // window, and the reference takes them all) is listed and solved again below with room for a full window
             auto launch_block = [&](int blocks, int maxd, const int32_t *list, const int32_t *count) -> int {
                 const size_t need = (size_t)blocks * maxd * (4 + 8 + 8);
-                if (t->scratch_bytes < need) {
-                    if (t->scratch) { HIP_TRY(hipFree(t->scratch)); t->device_bytes -= (int64_t)t->scratch_bytes; }
-                    HIP_TRY(dev_malloc((void **)&t->scratch, need));
-                    t->scratch_bytes = need; t->device_bytes += (int64_t)need;
-                }
+                PYDEM_TRY(tile_reserve(t, &t->scratch, &t->scratch_bytes, need, need, false));
                 double *g_dxy = (double *)t->scratch;
                 double *g_sv = g_dxy + (size_t)blocks * maxd;
                 int32_t *g_dl = (int32_t *)(g_sv + (size_t)blocks * maxd);
@@ -1583,12 +1582,13 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
     if (ne > 0) {
         if (t->pits.sorted_cap < ne) {
             // `ne` counts the partly used chunks of the wavefronts as well and moves by a few hundred from run to run: sized in
-            // steps of 64 Ki entries, or every run of the same tile would ask the plane cache (exact sizes, tile.hip) for
+            // steps of 64 Ki entries, or every run of the same tile would ask the plane cache (exact sizes, devmem.hip) for
             // blocks of a size it has not seen
             const size_t sc = ((size_t)ne + 65535) & ~(size_t)65535;
-            PYDEM_TRY(dev_realloc(t, &t->pits.src, sc)); PYDEM_TRY(dev_realloc(t, &t->pits.dst, sc));
-            PYDEM_TRY(dev_realloc(t, &t->pits.w, sc)); PYDEM_TRY(dev_realloc(t, &t->pits.in_src, sc));
-            PYDEM_TRY(dev_realloc(t, &t->pits.in_dst, sc)); PYDEM_TRY(dev_realloc(t, &t->pits.in_w, sc));
+            t->pits.sorted_cap = 0;
+            PYDEM_TRY(view_grow(t, &t->pits.src, sc)); PYDEM_TRY(view_grow(t, &t->pits.dst, sc));
+            PYDEM_TRY(view_grow(t, &t->pits.w, sc)); PYDEM_TRY(view_grow(t, &t->pits.in_src, sc));
+            PYDEM_TRY(view_grow(t, &t->pits.in_dst, sc)); PYDEM_TRY(view_grow(t, &t->pits.in_w, sc));
             t->pits.sorted_cap = (int64_t)sc;
         }
         // one persistent scratch block (allocating and freeing eight buffers per call costs more than the sorts)
@@ -1598,11 +1598,7 @@ int stage_pits(pydem_tile *t, const pydem_options *opt)
         const size_t ne8 = ((size_t)ne * 8 + 255) & ~(size_t)255, ne4 = ((size_t)ne * 4 + 255) & ~(size_t)255;
         const size_t tmp_al = (tmp_bytes + 255) & ~(size_t)255;
         const size_t need_sort = 4 * ne8 + 3 * ne4 + 2 * tmp_al + 256;          // (two scratch areas: the sorts run side by side)
-        if (t->pits.sort_bytes < need_sort) {
-            if (t->pits.sort_buf) { HIP_TRY(hipFree(t->pits.sort_buf)); t->device_bytes -= (int64_t)t->pits.sort_bytes; }
-            HIP_TRY(dev_malloc((void **)&t->pits.sort_buf, need_sort + need_sort / 4));
-            t->pits.sort_bytes = need_sort + need_sort / 4; t->device_bytes += (int64_t)t->pits.sort_bytes;
-        }
+        PYDEM_TRY(tile_reserve(t, &t->pits.sort_buf, &t->pits.sort_bytes, need_sort, need_sort + need_sort / 4, false));
         char *sb = (char *)t->pits.sort_buf;
         uint64_t *k1 = (uint64_t *)sb, *k2 = (uint64_t *)(sb + ne8), *k1s = (uint64_t *)(sb + 2 * ne8), *k2s = (uint64_t *)(sb + 3 * ne8);
         int32_t *idx = (int32_t *)(sb + 4 * ne8), *i1 = (int32_t *)(sb + 4 * ne8 + ne4), *i2 = (int32_t *)(sb + 4 * ne8 + 2 * ne4);

@@ -2,10 +2,8 @@
 #include "internal.h"
 #include "uca_graph.h"      // CI_STATIC_MASK, CS_FLAT_SAVE
 #include <cmath>
-#include <math.h>
 #include <stdarg.h>
 #include <string.h>
-#include <stdlib.h>
 
 static thread_local char g_err[1024] = "";
 
@@ -15,216 +13,6 @@ void pydem_set_error(const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
-}
-
-// ---- planes of destroyed tiles are kept for the next tile of the same shape ------------------------------------------
-// A fresh DEMProcessor per elevation file is how the reference is used, and a 16384^2 tile is a dozen 0.25-2 GiB planes:
-// mapping them anew costs the drop-in call more than its kernels (measured: ~240 ms of hipMalloc inside a 54-ms calc_twi).
-// Blocks of 1 MiB and more that tile_alloc handed out go on a per-device free list when their tile is destroyed and are
-// handed out again on an exact size match (the contents are whatever the last owner left: no stage relies on fresh
-// memory).  PYDEM_PLANE_CACHE_GB bounds what is kept per device (default 32, 0 = off; the least recently returned blocks are evicted first); pydem_hip_release_scratch and a
-// failing hipMalloc empty the lists.
-#include <map>
-#include <mutex>
-#include <unordered_map>
-namespace {
-struct FreeBlock { void *p; uint64_t stamp; };      // stamp: when the block was given back (the oldest is evicted first)
-struct PlaneCache {
-    std::mutex mu;
-    std::multimap<size_t, FreeBlock> free_blocks;
-    uint64_t clock = 0;
-    std::unordered_map<void *, size_t> live;          // blocks handed out by tile_alloc (size known at destroy time)
-    size_t kept = 0;
-};
-std::mutex g_pc_table;
-std::map<int, PlaneCache *> g_pc;
-PlaneCache *plane_cache(int device)
-{
-    std::lock_guard<std::mutex> g(g_pc_table);
-    PlaneCache *&c = g_pc[device];
-    if (!c) c = new PlaneCache();
-    return c;
-}
-size_t plane_cache_limit()
-{
-    // default 32 GiB: the planes of one 16384^2 tile (24.7 GB) -- what the drop-in pattern "a fresh DEMProcessor per file" reuses;
-    // fractions of a GB are honoured, a negative value means 0 (off)
-    static const size_t lim = [] {
-        const char *e = getenv("PYDEM_PLANE_CACHE_GB");
-        const double gb = e ? atof(e) : 32.0;
-        return (size_t)((gb > 0.0 ? gb : 0.0) * (double)((size_t)1 << 30));
-    }();
-    return lim;
-}
-// (c->mu held) take the least recently returned blocks off the lists until `room` more bytes fit under the limit; the caller
-// frees them AFTER it has let go of the lock (hipFree synchronises the device)
-void plane_cache_evict(PlaneCache *c, size_t room, std::vector<void *> &victims)
-{
-    const size_t lim = plane_cache_limit();
-    while (!c->free_blocks.empty() && c->kept + room > lim) {
-        auto old = c->free_blocks.begin();
-        for (auto it = c->free_blocks.begin(); it != c->free_blocks.end(); ++it) if (it->second.stamp < old->second.stamp) old = it;
-        victims.push_back(old->second.p);
-        c->kept -= old->first;
-        c->free_blocks.erase(old);
-    }
-}
-constexpr size_t PLANE_MIN = (size_t)1 << 20;
-void plane_cache_flush(int device)
-{
-    PlaneCache *c = plane_cache(device);
-    std::lock_guard<std::mutex> g(c->mu);
-    for (auto &kv : c->free_blocks) (void)hipFree(kv.second.p);
-    c->free_blocks.clear(); c->kept = 0;
-}
-}  // namespace
-
-void *plane_take(int device, size_t bytes)
-{
-    std::vector<void *> victims;                     // (PYDEM_PLANE_EVICT_ON_MISS only; freed once the lock is released)
-    if (bytes >= PLANE_MIN && plane_cache_limit()) {
-        PlaneCache *c = plane_cache(device);
-        std::lock_guard<std::mutex> g(c->mu);
-        auto it = c->free_blocks.find(bytes);
-        if (it != c->free_blocks.end()) {
-            void *q = it->second.p;
-            c->free_blocks.erase(it); c->kept -= bytes;
-            c->live[q] = bytes;
-            return q;
-        }
-        // (a size the lists do not hold: nothing is evicted here -- the blocks on the lists are those of the tile destroyed
-        // last, i.e. what the tile being built asks for next; dead sizes leave when plane_give needs their room, and a failing
-        // hipMalloc empties the lists.  PYDEM_PLANE_EVICT_ON_MISS=1: the round-5 behaviour, for A/B runs)
-        static const bool on_miss = [] { const char *e = getenv("PYDEM_PLANE_EVICT_ON_MISS"); return e && atoi(e) > 0; }();
-        if (on_miss) plane_cache_evict(c, bytes, victims);
-    }
-    for (void *v : victims) (void)hipFree(v);
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes);
-    {   // PYDEM_PLANE_DEBUG=1: one line per block that is mapped anew (a steady state maps nothing)
-        static const bool dbg = [] { const char *d = getenv("PYDEM_PLANE_DEBUG"); return d && atoi(d) > 0; }();
-        if (dbg) fprintf(stderr, "[pydem] plane_take: hipMalloc(%zu)\n", bytes);
-    }
-    if (e != hipSuccess) {                          // the free lists may hold what is missing
-        (void)hipGetLastError();
-        plane_cache_flush(device);
-        e = hipMalloc(&q, bytes);
-    }
-    if (e != hipSuccess) { pydem_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return nullptr; }
-    if (bytes >= PLANE_MIN && plane_cache_limit()) {
-        PlaneCache *c = plane_cache(device);
-        std::lock_guard<std::mutex> g(c->mu);
-        c->live[q] = bytes;
-    }
-    return q;
-}
-
-void plane_give(int device, void *q)
-{
-    if (!q) return;
-    PlaneCache *c = plane_cache(device);
-    std::vector<void *> victims;
-    bool kept = false;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        auto it = c->live.find(q);
-        if (it != c->live.end()) {
-            const size_t bytes = it->second;
-            c->live.erase(it);
-            if (bytes <= plane_cache_limit()) {
-                plane_cache_evict(c, bytes, victims);
-                c->free_blocks.emplace(bytes, FreeBlock{q, ++c->clock}); c->kept += bytes;
-                kept = true;
-            }
-        }
-    }
-    for (void *v : victims) (void)hipFree(v);
-    if (!kept) (void)hipFree(q);
-}
-
-// hipMalloc for everything else the library maps on a device (scratch, arenas, record buffers): when it fails the free lists
-// of the current device are emptied and the call repeated
-hipError_t dev_malloc(void **p, size_t bytes)
-{
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        int device = 0;
-        (void)hipGetLastError();
-        if (hipGetDevice(&device) == hipSuccess) { plane_cache_flush(device); e = hipMalloc(p, bytes); }
-    }
-    return e;
-}
-
-template <typename T>
-int tile_alloc(pydem_tile *t, T **p, size_t count)
-{
-    if (*p) return 0;
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    void *q = plane_take(t->device, bytes);
-    if (!q) return -1;
-    t->device_bytes += (int64_t)bytes;
-    *p = (T *)q;
-    return 0;
-}
-template int tile_alloc<double>(pydem_tile *, double **, size_t);
-template int tile_alloc<uint8_t>(pydem_tile *, uint8_t **, size_t);
-template int tile_alloc<int8_t>(pydem_tile *, int8_t **, size_t);
-template int tile_alloc<int32_t>(pydem_tile *, int32_t **, size_t);
-template int tile_alloc<uint32_t>(pydem_tile *, uint32_t **, size_t);
-template int tile_alloc<RowTab>(pydem_tile *, RowTab **, size_t);
-template int tile_alloc<uint16_t>(pydem_tile *, uint16_t **, size_t);
-
-// ---- per-device scratch arena of the conditioning stages (internal.h)
-#include <map>
-#include <time.h>
-#include <mutex>
-namespace {
-struct DevArena { std::mutex busy; void *p = nullptr; size_t bytes = 0; };
-std::mutex g_arena_table;
-std::map<int, DevArena *> g_arenas;
-DevArena *arena_of(int device)
-{
-    std::lock_guard<std::mutex> g(g_arena_table);
-    DevArena *&a = g_arenas[device];
-    if (!a) a = new DevArena();
-    return a;
-}
-}  // namespace
-
-int arena_acquire(int device, ArenaLease *L)
-{
-    DevArena *a = arena_of(device);
-    a->busy.lock();
-    L->device = device; L->arena = a; L->base = (char *)a->p; L->bytes = a->bytes; L->off = 0; L->want = 0; L->held = true;
-    return 0;
-}
-
-void *arena_take(ArenaLease *L, size_t bytes)
-{
-    const size_t need = (bytes + 255) & ~(size_t)255;
-    L->want += need ? need : 256;
-    if (L->base && L->off + need <= L->bytes) { void *q = L->base + L->off; L->off += need ? need : 256; return q; }
-    void *q = nullptr;
-    const hipError_t e = dev_malloc(&q, need ? need : 256);
-    if (e != hipSuccess) { pydem_set_error("hipMalloc(%zu bytes) failed: %s", need, hipGetErrorString(e)); return nullptr; }
-    L->extra.push_back(q);
-    return q;
-}
-
-ArenaLease::~ArenaLease()
-{
-    if (!held) return;
-    DevArena *a = static_cast<DevArena *>(arena);
-    (void)hipSetDevice(device);
-    for (void *q : extra) (void)hipFree(q);
-    if (want > a->bytes) {              // next time everything fits
-        if (a->p) (void)hipFree(a->p);
-        a->p = nullptr; a->bytes = 0;
-        void *q = nullptr;
-        if (dev_malloc(&q, want + want / 8) == hipSuccess) { a->p = q; a->bytes = want + want / 8; }
-    }
-    a->busy.unlock();
 }
 
 namespace {
@@ -334,144 +122,11 @@ int ensure_field(pydem_tile *t, int field)
 {
     void **pp; size_t elem;
     PYDEM_TRY(field_ptr(t, field, &pp, &elem));
-    if (*pp) return 0;
     if (elem == 8) return tile_alloc(t, (double **)pp, (size_t)t->NN);
     return tile_alloc(t, (uint8_t **)pp, (size_t)t->NN);
 }
 
 }  // namespace
-
-int tile_pinned(pydem_tile *t, size_t bytes, void **out)
-{
-    if (t->h_stage_bytes < bytes) {
-        if (t->h_stage) { (void)hipHostFree(t->h_stage); t->h_stage = nullptr; t->h_stage_bytes = 0; }
-        const size_t want = bytes + bytes / 4 + 4096;
-        HIP_TRY(hipHostMalloc(&t->h_stage, want, hipHostMallocDefault));
-        t->h_stage_bytes = want;
-    }
-    *out = t->h_stage;
-    return 0;
-}
-
-// ---- whole-plane transfers between pageable host arrays and the device ------------------------------------------------
-// A plain hipMemcpy of a pageable array pins the caller's pages on the fly: measured here at ~3 GB/s for a fresh 2 GiB array
-// (0.7 s for the 16384^2 elevations).  Planes of XFER_MIN bytes or more go through per-device pinned chunks instead: XFER_T
-// host threads each copy their chunks between the caller's array and their two pinned buffers while their own stream moves
-// the previous chunk over PCIe (the threads also take the first-touch page faults of a fresh destination array in
-// parallel).  PYDEM_XFER_THREADS=0 restores the plain copy.
-#include <thread>
-#include <sys/mman.h>
-namespace {
-constexpr size_t XFER_CHUNK = (size_t)8 << 20;
-constexpr size_t XFER_MIN = (size_t)32 << 20;
-constexpr int XFER_TMAX = 16;
-struct XferLane { void *pin[2] = {nullptr, nullptr}; hipStream_t stream = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; };
-struct XferPool { std::mutex busy; XferLane lane[XFER_TMAX]; int ready = 0; };
-std::mutex g_xfer_table;
-std::map<int, XferPool *> g_xfer;
-
-int xfer_threads()
-{
-    static const int n = [] {
-        const char *e = getenv("PYDEM_XFER_THREADS");
-        int v = e ? atoi(e) : 8;
-        return v < 0 ? 0 : (v > XFER_TMAX ? XFER_TMAX : v);
-    }();
-    return n;
-}
-
-int xfer_pool(int device, int T, XferPool **out)
-{
-    XferPool *P;
-    {
-        std::lock_guard<std::mutex> g(g_xfer_table);
-        XferPool *&p = g_xfer[device];
-        if (!p) p = new XferPool();
-        P = p;
-    }
-    *out = P;
-    return 0;
-}
-
-int xfer_prepare(XferPool *P, int T)      // under P->busy
-{
-    for (int k = P->ready; k < T; ++k) {
-        XferLane &L = P->lane[k];
-        for (int b = 0; b < 2; ++b) {
-            if (!L.pin[b]) HIP_TRY(hipHostMalloc(&L.pin[b], XFER_CHUNK, hipHostMallocDefault));
-            if (!L.ev[b]) HIP_TRY(hipEventCreateWithFlags(&L.ev[b], hipEventDisableTiming));
-        }
-        if (!L.stream) HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-        P->ready = k + 1;
-    }
-    return 0;
-}
-
-// one lane's share of the plane: chunks k, k + T, ...
-hipError_t xfer_lane_run(int device, XferLane &L, char *dev, char *host, size_t bytes, int k, int T, bool to_host)
-{
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return e;
-    const size_t nchunk = (bytes + XFER_CHUNK - 1) / XFER_CHUNK;
-    size_t prev_off = 0, prev_len = 0; int prev_b = -1;
-    int it = 0;
-    for (size_t c = (size_t)k; c < nchunk; c += (size_t)T, ++it) {
-        const int b = it & 1;
-        const size_t off = c * XFER_CHUNK, len = (bytes - off < XFER_CHUNK) ? bytes - off : XFER_CHUNK;
-        if (!to_host) {
-            if (it >= 2 && (e = hipEventSynchronize(L.ev[b])) != hipSuccess) return e;     // the buffer's previous chunk has left
-            memcpy(L.pin[b], host + off, len);
-            if ((e = hipMemcpyAsync(dev + off, L.pin[b], len, hipMemcpyHostToDevice, L.stream)) != hipSuccess) return e;
-            if ((e = hipEventRecord(L.ev[b], L.stream)) != hipSuccess) return e;
-        } else {
-            if ((e = hipMemcpyAsync(L.pin[b], dev + off, len, hipMemcpyDeviceToHost, L.stream)) != hipSuccess) return e;
-            if ((e = hipEventRecord(L.ev[b], L.stream)) != hipSuccess) return e;
-            if (prev_b >= 0) {
-                if ((e = hipEventSynchronize(L.ev[prev_b])) != hipSuccess) return e;
-                memcpy(host + prev_off, L.pin[prev_b], prev_len);
-            }
-            prev_b = b; prev_off = off; prev_len = len;
-        }
-    }
-    if (to_host && prev_b >= 0) {
-        if ((e = hipEventSynchronize(L.ev[prev_b])) != hipSuccess) return e;
-        memcpy(host + prev_off, L.pin[prev_b], prev_len);
-    }
-    return hipStreamSynchronize(L.stream);
-}
-}  // namespace
-
-// copy `bytes` between a device plane and a (pageable) host array; the tile's stream is drained first and the call returns
-// with the transfer complete
-int tile_plane_copy(pydem_tile *t, void *dev, void *host, size_t bytes, bool to_host)
-{
-    const int T = xfer_threads();
-    if (T == 0 || bytes < XFER_MIN) {
-        if (to_host) HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, t->stream));
-        else HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        return 0;
-    }
-    HIP_TRY(hipStreamSynchronize(t->stream));          // what the plane holds (or what still reads it) is settled
-    if (to_host) {
-        // a fresh destination array is faulted in by the copy threads: ask for huge pages where the kernel gives them on request
-        const uintptr_t a = ((uintptr_t)host + 4095) & ~(uintptr_t)4095, b = ((uintptr_t)host + bytes) & ~(uintptr_t)4095;
-        if (b > a) (void)madvise((void *)a, b - a, MADV_HUGEPAGE);
-    }
-    XferPool *P;
-    PYDEM_TRY(xfer_pool(t->device, T, &P));
-    std::lock_guard<std::mutex> g(P->busy);
-    PYDEM_TRY(xfer_prepare(P, T));
-    hipError_t err[XFER_TMAX];
-    std::thread th[XFER_TMAX];
-    for (int k = 1; k < T; ++k)
-        th[k] = std::thread([&, k] { err[k] = xfer_lane_run(t->device, P->lane[k], (char *)dev, (char *)host, bytes, k, T, to_host); });
-    err[0] = xfer_lane_run(t->device, P->lane[0], (char *)dev, (char *)host, bytes, 0, T, to_host);
-    for (int k = 1; k < T; ++k) th[k].join();
-    for (int k = 0; k < T; ++k)
-        if (err[k] != hipSuccess) { pydem_set_error("plane transfer: %s", hipGetErrorString(err[k])); return -1; }
-    return 0;
-}
 
 int ensure_fields(pydem_tile *t, std::initializer_list<int> fields)
 {
@@ -485,42 +140,7 @@ const char *pydem_hip_last_error(void) { return g_err; }
 
 int pydem_hip_release_scratch(void)
 {
-    // lock order: never `busy` under the table lock (a lease holds `busy` for the length of a conditioning stage; records are
-    // never deleted, so the snapshot stays valid)
-    std::vector<std::pair<int, DevArena *>> all;
-    {
-        std::lock_guard<std::mutex> g(g_arena_table);
-        for (auto &kv : g_arenas) all.push_back(kv);
-    }
-    for (auto &kv : all) {
-        std::lock_guard<std::mutex> b(kv.second->busy);
-        if (kv.second->p) { (void)hipSetDevice(kv.first); (void)hipFree(kv.second->p); kv.second->p = nullptr; kv.second->bytes = 0; }
-    }
-    std::vector<int> devs;
-    {
-        std::lock_guard<std::mutex> g(g_pc_table);
-        for (auto &kv : g_pc) devs.push_back(kv.first);
-    }
-    for (int d : devs) { (void)hipSetDevice(d); plane_cache_flush(d); }
-    // ... and the pinned chunks / streams of the whole-plane transfers (they come back with the next large transfer)
-    std::vector<std::pair<int, XferPool *>> pools;
-    {
-        std::lock_guard<std::mutex> g(g_xfer_table);
-        for (auto &kv : g_xfer) pools.push_back(kv);
-    }
-    for (auto &kv : pools) {
-        std::lock_guard<std::mutex> b(kv.second->busy);
-        (void)hipSetDevice(kv.first);
-        for (int k = 0; k < kv.second->ready; k++) {
-            XferLane &L = kv.second->lane[k];
-            for (int q = 0; q < 2; q++) {
-                if (L.pin[q]) { (void)hipHostFree(L.pin[q]); L.pin[q] = nullptr; }
-                if (L.ev[q]) { (void)hipEventDestroy(L.ev[q]); L.ev[q] = nullptr; }
-            }
-            if (L.stream) { (void)hipStreamDestroy(L.stream); L.stream = nullptr; }
-        }
-        kv.second->ready = 0;
-    }
+    devmem_release_all();
     return 0;
 }
 
@@ -548,13 +168,8 @@ int pydem_hip_device_name(int device, char *buf, int buflen)
     return 0;
 }
 
-int pydem_tile_create(int64_t n_rows, int64_t n_cols, int device, pydem_tile **out)
+static int tile_init(pydem_tile *t)
 {
-    if (n_rows < 3 || n_cols < 3) { pydem_set_error("tile must be at least 3x3 (got %lld x %lld)", (long long)n_rows, (long long)n_cols); return -2; }
-    if (n_rows * n_cols >= (int64_t)INT32_MAX) { pydem_set_error("tile too large for int32 cell ids"); return -2; }
-    HIP_TRY(hipSetDevice(device));
-    pydem_tile *t = new pydem_tile();
-    t->n = n_rows; t->m = n_cols; t->NN = n_rows * n_cols; t->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
@@ -563,6 +178,18 @@ int pydem_tile_create(int64_t n_rows, int64_t n_cols, int device, pydem_tile **o
     for (int i = 0; i < 8; i++) HIP_TRY(hipEventCreate(&t->ev[i]));
     PYDEM_TRY(tile_alloc(t, &t->counters, 64));
     HIP_TRY(hipHostMalloc((void **)&t->h_counters, 64 * sizeof(int32_t), hipHostMallocDefault));
+    return 0;
+}
+
+int pydem_tile_create(int64_t n_rows, int64_t n_cols, int device, pydem_tile **out)
+{
+    if (n_rows < 3 || n_cols < 3) { pydem_set_error("tile must be at least 3x3 (got %lld x %lld)", (long long)n_rows, (long long)n_cols); return -2; }
+    if (n_rows * n_cols >= (int64_t)INT32_MAX) { pydem_set_error("tile too large for int32 cell ids"); return -2; }
+    HIP_TRY(hipSetDevice(device));
+    pydem_tile *t = new pydem_tile();
+    t->n = n_rows; t->m = n_cols; t->NN = n_rows * n_cols; t->device = device;
+    const int rc = tile_init(t);
+    if (rc != 0) { pydem_tile_destroy(t); return rc; }      // (the half-built handle goes; the error text stays)
     *out = t;
     return 0;
 }
@@ -571,20 +198,11 @@ int pydem_tile_destroy(pydem_tile *t)
 {
     if (!t) return 0;
     (void)hipSetDevice(t->device);
-    (void)hipStreamSynchronize(t->stream);
+    if (t->stream) (void)hipStreamSynchronize(t->stream);
     // (a stage that returned early between the fork and the join of the side stream may have left kernels there that still
     // write edge_todo / todo_work / prop: the planes go to the free lists -- i.e. to the next tile -- only once both streams are idle)
     if (t->stream2) (void)hipStreamSynchronize(t->stream2);
-    void *ptrs[] = {t->elev, t->mag, t->dir, t->prop, t->uca, t->twi, t->weight, t->uca_w, t->flats, t->edge_todo, t->edge_done,
-                    t->flat0, t->section, t->dX, t->dY, t->dX2, t->dY2, t->rowtab, t->sec_theta, t->row_area,
-                    t->todo_work, t->cinfo, t->queue[0], t->queue[1], t->labels, t->flatlist,
-                    t->counters, t->scratch, t->pits.src, t->pits.dst, t->pits.w, t->pits.in_src,
-                    t->pits.in_dst, t->pits.in_w, t->pits.raw_src, t->pits.raw_dst, t->pits.raw_w,
-                    t->estamp, t->edelta, t->p_delta, t->s_data, t->p_flags, t->s_flags, t->line_stage, t->contrib,
-                    t->eseed, t->lines_stage, t->pits.sort_buf, t->nd_rec, t->cond_mem, t->cb_mem[0], t->cb_mem[1], t->cb_mem[2],
-                    t->dd_out, t->dd_queue, t->dd_mask, t->dd_ctr, t->ra_seed, t->fa_mult, t->fa_cap, t->fa_inflow,
-                    t->sn_recv, t->sn_code, t->ta_sc};
-    for (void *p : ptrs) if (p) plane_give(t->device, p);          // (blocks that did not come from tile_alloc are freed)
+    tile_release_all(t);
     if (t->h_counters) (void)hipHostFree(t->h_counters);
     if (t->h_strip_d) (void)hipHostFree(t->h_strip_d);
     if (t->h_stage) (void)hipHostFree(t->h_stage);
@@ -676,11 +294,7 @@ int pydem_tile_upload(pydem_tile *t, int field, const void *src, int dtype)
     } else {
         if (elem != 8) { pydem_set_error("dtype conversion is only supported for float64 fields"); return -2; }
         const size_t bytes = (size_t)t->NN * ds;
-        if (t->scratch_bytes < bytes) {
-            if (t->scratch) { HIP_TRY(hipFree(t->scratch)); t->device_bytes -= (int64_t)t->scratch_bytes; }
-            HIP_TRY(dev_malloc(&t->scratch, bytes));
-            t->scratch_bytes = bytes; t->device_bytes += (int64_t)bytes;
-        }
+        PYDEM_TRY(tile_reserve(t, &t->scratch, &t->scratch_bytes, bytes, bytes, false));
         PYDEM_TRY(tile_plane_copy(t, t->scratch, const_cast<void *>(src), bytes, false));
         const int grid = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
         double *dst = (double *)*pp;
@@ -744,7 +358,7 @@ static int line_copy(pydem_tile *t, int field, int axis, int64_t index, void *ho
         else HIP_TRY(hipMemcpyAsync(row, host, (size_t)t->m * elem, hipMemcpyHostToDevice, t->stream));
     } else {
         const int64_t cnt = t->n;
-        if (!t->line_stage) PYDEM_TRY(tile_alloc(t, &t->line_stage, (size_t)(t->n > t->m ? t->n : t->m)));
+        PYDEM_TRY(tile_alloc(t, &t->line_stage, (size_t)(t->n > t->m ? t->n : t->m)));
         const int g = (int)(cdiv(cnt, 256) < 64 ? cdiv(cnt, 256) : 64);
         char *col = base + (size_t)index * elem;
         if (to_host) {
@@ -773,12 +387,7 @@ int pydem_tile_get_lines(pydem_tile *t, int count, const int *fields, const int 
 {
     HIP_TRY(hipSetDevice(t->device));
     const size_t L = (size_t)(t->n > t->m ? t->n : t->m);
-    if (count > 0 && t->lines_cap < count) {
-        if (t->lines_stage) { HIP_TRY(hipFree(t->lines_stage)); t->device_bytes -= (int64_t)((size_t)t->lines_cap * L * 8); }
-        const int cap = count < 16 ? 16 : count;
-        HIP_TRY(dev_malloc(&t->lines_stage, (size_t)cap * L * 8));
-        t->lines_cap = cap; t->device_bytes += (int64_t)((size_t)cap * L * 8);
-    }
+    if (count > 0) PYDEM_TRY(tile_reserve(t, &t->lines_stage, &t->lines_bytes, (size_t)count * L * 8, (size_t)(count < 16 ? 16 : count) * L * 8, false));
     void *pin_v = nullptr;                                  // (pinned staging: the callers' arrays are pageable)
     PYDEM_TRY(tile_pinned(t, (size_t)(count > 0 ? count : 1) * L * 8, &pin_v));
     char *pin = (char *)pin_v;
@@ -1042,13 +651,6 @@ static bool same_graph_options(const pydem_options &a, const pydem_options &b)
            a.drain_pits_max_iter == b.drain_pits_max_iter && a.drain_pits_max_dist == b.drain_pits_max_dist && xy;
 }
 
-namespace {
-struct DevScratch {                     // a temporary device block that is freed on every way out
-    void *p = nullptr;
-    ~DevScratch() { if (p) (void)hipFree(p); }
-};
-}
-
 int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area)
 {
     HIP_TRY(hipSetDevice(t->device));
@@ -1060,7 +662,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
     // (graph_valid pairs a graph with the PATCHED planes, as pydem_uca leaves them), so every call on such a tile starts from
     // the same surface and a later pydem_uca / edge round builds its own graph.
     const bool own_graph = !t->graph_valid || !same_graph_options(t->graph_opt, *opt);
-    DevScratch save, planes;
+    DevTemp save, planes;
     struct Kept { void *dst; size_t bytes; size_t off; };
     std::vector<Kept> kept;             // resident results the graph stage overwrites (a tile where pydem_uca ran with other options)
     int32_t *save_cells = nullptr;
@@ -1080,7 +682,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
         HIP_TRY(hipStreamSynchronize(t->stream));
         nsave = (int64_t)hn;
         if (nsave > 0) {
-            HIP_TRY(dev_malloc(&save.p, (size_t)nsave * 12));
+            PYDEM_TRY(save.alloc((size_t)nsave * 12));
             save_vals = (double *)save.p;
             save_cells = (int32_t *)((char *)save.p + (size_t)nsave * 8);
             HIP_TRY(hipMemsetAsync(cnt, 0, 8, t->stream));
@@ -1093,7 +695,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
         if (t->have[PYDEM_EDGE_TODO]) { kept.push_back({t->edge_todo, (size_t)t->NN, off}); off += (size_t)t->NN; }
         off = (off + 255) & ~(size_t)255;
         if (t->have[PYDEM_PROPORTION]) { kept.push_back({t->prop, (size_t)t->NN * 8, off}); off += (size_t)t->NN * 8; }
-        if (off) HIP_TRY(dev_malloc(&planes.p, off));
+        if (off) PYDEM_TRY(planes.alloc(off));
         for (const Kept &k : kept)
             HIP_TRY(hipMemcpyAsync((char *)planes.p + k.off, k.dst, k.bytes, hipMemcpyDeviceToDevice, t->stream));
         t->graph_valid = false;

@@ -2087,11 +2087,7 @@ static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
     // scratch: tile_done bytes | per-tile "listed for pass" stamps | two tile lists | open cells per tile
     const size_t tiles_pad = ((size_t)tiles_total + 255) & ~(size_t)255;
     const size_t scratch_need = tiles_pad * (1 + 4 + 4 + 4 + 4 + 4) + 64 * sizeof(int32_t);     // ... | block offsets of the symbolic tiles | K5f counters
-    if (t->scratch_bytes < scratch_need) {
-        if (t->scratch) { HIP_TRY(hipFree(t->scratch)); t->device_bytes -= (int64_t)t->scratch_bytes; }
-        HIP_TRY(dev_malloc((void **)&t->scratch, scratch_need));
-        t->scratch_bytes = scratch_need; t->device_bytes += (int64_t)scratch_need;
-    }
+    PYDEM_TRY(tile_reserve(t, &t->scratch, &t->scratch_bytes, scratch_need, scratch_need, false));
     uint8_t *tile_done = (uint8_t *)t->scratch;
     int32_t *tile_flag = (int32_t *)(tile_done + tiles_pad);
     int32_t *tile_list[2] = {tile_flag + tiles_pad, tile_flag + 2 * tiles_pad};
@@ -2198,10 +2194,10 @@ static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
                 fprintf(stderr, "pydem: circular drainage with %lld unfinished cells: the re-seed loop runs on the host\n", (long long)unfinished);
                 if (unfinished > INT32_MAX / 2) { pydem_set_error("circular drainage: %lld unfinished cells", (long long)unfinished); return -5; }
                 const int32_t nU = (int32_t)unfinished;
-                void *d_tmp = nullptr;
-                HIP_TRY(dev_malloc((void **)&d_tmp, (size_t)nU * (sizeof(ReseedCell) + sizeof(ReseedHost))));
-                ReseedCell *U2 = (ReseedCell *)d_tmp;
-                ReseedHost *dH = (ReseedHost *)((char *)d_tmp + (size_t)nU * sizeof(ReseedCell));
+                DevTemp d_tmp;
+                PYDEM_TRY(d_tmp.alloc((size_t)nU * (sizeof(ReseedCell) + sizeof(ReseedHost))));
+                ReseedCell *U2 = d_tmp.as<ReseedCell>();
+                ReseedHost *dH = (ReseedHost *)(d_tmp.as<char>() + (size_t)nU * sizeof(ReseedCell));
                 HIP_TRY(hipMemsetAsync(rc, 0, 3 * sizeof(int32_t), t->stream));
                 hipLaunchKernelGGL(k_reseed_collect, dim3(grid_for(t->NN, 4096)), dim3(256), 0, t->stream, A, U2, rc, nU, (const double *)t->elev, rc + 1);
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reseed_gather<WT>), dim3(grid_for(nU, 1024)), dim3(256), 0, t->stream, A, (const ReseedCell *)U2, nU, (const double *)t->elev, dH);
@@ -2228,7 +2224,6 @@ static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
                 HIP_TRY(hipMemcpy(dH, back.data(), (size_t)nU * sizeof(ReseedBack), hipMemcpyHostToDevice));
                 hipLaunchKernelGGL(k_reseed_scatter, dim3(grid_for(nU, 1024)), dim3(256), 0, t->stream, A, (const ReseedBack *)dH, nU, pass);
                 HIP_TRY(hipStreamSynchronize(t->stream));
-                HIP_TRY(hipFree(d_tmp));
                 t->h_counters[CS_PROCESSED] += (int32_t)n_done;
                 HIP_TRY(hipMemcpy(t->counters + CS_PROCESSED, t->h_counters + CS_PROCESSED, sizeof(int32_t), hipMemcpyHostToDevice));
                 if (getenv("PYDEM_SWEEP_DEBUG")) fprintf(stderr, "circular drainage: %lld unfinished cells, %lld finished by the re-seed replay on the host\n", (long long)unfinished, (long long)n_done);

@@ -1304,12 +1304,7 @@ static int einc_prepare(pydem_tile *t, IncArgs &E)
     { const char *e = getenv("PYDEM_EINC_COMPACT_MAX"); if (e) compact_max = atoll(e); }
     t->einc_compact = nd <= compact_max;
     if (t->einc_compact) {
-        if (nd > t->nd_cap) {
-            if (t->nd_rec) { HIP_TRY(hipFree(t->nd_rec)); t->device_bytes -= t->nd_cap * (int64_t)sizeof(NDRec); }
-            const int64_t cap = nd + nd / 8 + 1024;
-            HIP_TRY(dev_malloc((void **)&t->nd_rec, (size_t)cap * sizeof(NDRec)));
-            t->nd_cap = cap; t->device_bytes += cap * (int64_t)sizeof(NDRec);
-        }
+        PYDEM_TRY(tile_reserve(t, &t->nd_rec, &t->nd_bytes, (size_t)nd * sizeof(NDRec), (size_t)(nd + nd / 8 + 1024) * sizeof(NDRec), false));
         t->nd = (int32_t)nd;
         CIncArgs C;
         PYDEM_TRY(cinc_args(t, C));
@@ -1387,10 +1382,10 @@ static int cond_build_host(pydem_tile *t)
     if (C.G.n_pit > 0)
         hipLaunchKernelGGL(k_cond_pit_edges, dim3(grid_for(nd, 1024)), dim3(256), 0, t->stream, C, (const double *)t->pits.w, d_pe, d_npe, pe_cap);
     CRecH *d_hr = reinterpret_cast<CRecH *>(t->queue[0]);
-    void *d_tmp = nullptr;
+    DevTemp d_tmp;
     if ((int64_t)nd * (int64_t)sizeof(CRecH) > t->NN * 4) {       // (small tiles that are mostly 'not done': the queue buffer is too short)
-        HIP_TRY(dev_malloc((void **)&d_tmp, (size_t)nd * sizeof(CRecH)));
-        d_hr = reinterpret_cast<CRecH *>(d_tmp);
+        PYDEM_TRY(d_tmp.alloc((size_t)nd * sizeof(CRecH)));
+        d_hr = d_tmp.as<CRecH>();
     }
     hipLaunchKernelGGL(k_cond_extract, dim3(grid_for(nd, 1024)), dim3(256), 0, t->stream, C, d_hr);
     void *pin_v = nullptr;
@@ -1403,7 +1398,6 @@ static int cond_build_host(pydem_tile *t)
     HIP_TRY(hipMemcpyAsync(h_npe, d_npe, sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipMemcpyAsync((void *)hr, d_hr, (size_t)nd * sizeof(CRecH), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
-    if (d_tmp) HIP_TRY(hipFree(d_tmp));
     const int32_t npe = *h_npe;
     if (npe > pe_cap) { g_cond_host_gave_up = "more pit edges among the records than its scratch holds"; return 0; }
     std::vector<CPitEdge> pe((size_t)npe);
@@ -1605,11 +1599,7 @@ static int cond_build_host(pydem_tile *t)
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_node = take((size_t)nw * sizeof(CNode)), o_edge = take((size_t)(ne + 1) * sizeof(CEdge)), o_slot = take((size_t)(nslot + 1) * 8),
                  o_q0 = take((size_t)nw * 4), o_q1 = take((size_t)nw * 4), o_nan = take(nan_cap * 4), o_cnt = take(64);
-    if (off > t->cond_bytes) {
-        if (t->cond_mem) { HIP_TRY(hipFree(t->cond_mem)); t->device_bytes -= (int64_t)t->cond_bytes; t->cond_mem = nullptr; t->cond_bytes = 0; }
-        HIP_TRY(dev_malloc((void **)&t->cond_mem, off + off / 8));
-        t->cond_bytes = off + off / 8; t->device_bytes += (int64_t)t->cond_bytes;
-    }
+    PYDEM_TRY(tile_reserve(t, &t->cond_mem, &t->cond_bytes, off, off + off / 8, false));
     char *base = (char *)t->cond_mem;
     t->cond_node = base + o_node; t->cond_edge = base + o_edge; t->cond_slot = (double *)(base + o_slot);
     t->cond_q0 = (int32_t *)(base + o_q0); t->cond_q1 = (int32_t *)(base + o_q1); t->cond_nanq = (int32_t *)(base + o_nan);
@@ -1636,11 +1626,9 @@ static int cond_build_host(pydem_tile *t)
 static int cb_reserve(pydem_tile *t, int which, size_t bytes)
 {
     if (t->cb_bytes[which] >= bytes) return 0;
-    if (t->cb_mem[which]) { HIP_TRY(hipStreamSynchronize(t->stream)); HIP_TRY(hipFree(t->cb_mem[which])); t->device_bytes -= (int64_t)t->cb_bytes[which]; t->cb_mem[which] = nullptr; t->cb_bytes[which] = 0; }
+    if (t->cb_mem[which]) HIP_TRY(hipStreamSynchronize(t->stream));      // (kernels of the build may still read the old block)
     const size_t want = (bytes + bytes / 4 + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1);     // (headroom + 1 MiB steps: run-to-run sizes move by a few records)
-    HIP_TRY(dev_malloc(&t->cb_mem[which], want));
-    t->cb_bytes[which] = want; t->device_bytes += (int64_t)want;
-    return 0;
+    return tile_reserve(t, &t->cb_mem[which], &t->cb_bytes[which], bytes, want, false);
 }
 
 struct CBump {
@@ -1744,7 +1732,8 @@ static int cond_build_device(pydem_tile *t, int *status)
     B.max_chain = cb_chain;
     int32_t *d_dbg = nullptr;                              // PYDEM_CB_DEBUG=1: per-level statistics of the sweep to stderr (diagnostic, one extra allocation)
     const int dbg_levels = 4096;
-    if (getenv("PYDEM_CB_DEBUG")) { HIP_TRY(hipMalloc((void **)&d_dbg, (size_t)dbg_levels * 4 * sizeof(int32_t))); HIP_TRY(hipMemsetAsync(d_dbg, 0, (size_t)dbg_levels * 4 * sizeof(int32_t), t->stream)); }
+    DevTemp dbg_mem;
+    if (getenv("PYDEM_CB_DEBUG")) { PYDEM_TRY(dbg_mem.alloc((size_t)dbg_levels * 4 * sizeof(int32_t))); d_dbg = dbg_mem.as<int32_t>(); HIP_TRY(hipMemsetAsync(d_dbg, 0, (size_t)dbg_levels * 4 * sizeof(int32_t), t->stream)); }
     B.dbg = d_dbg; B.level = 0;
     int levels_run = 0;
     void *pin_q = nullptr;
@@ -1766,7 +1755,6 @@ static int cond_build_device(pydem_tile *t, int *status)
     if (d_dbg) {
         std::vector<int32_t> hd((size_t)dbg_levels * 4);
         HIP_TRY(hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipFree(d_dbg));
         fprintf(stderr, "cb levels (frontier / largest merge / entries merged / deepest chain):");
         for (int l = 0; l < levels_run && l < dbg_levels; l++) { if (l % 8 == 0) fprintf(stderr, "\n  %4d:", l); fprintf(stderr, " %d/%d/%d/%d", hd[4 * l], hd[4 * l + 1], hd[4 * l + 2], hd[4 * l + 3]); }
         fprintf(stderr, "\n");
@@ -1807,12 +1795,7 @@ static int cond_build_device(pydem_tile *t, int *status)
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_node = take((size_t)nw * sizeof(CNode)), o_edge = take((size_t)(ne_all + 1) * sizeof(CEdge)), o_slot = take((size_t)(ne_all + 1) * 8),
                  o_q0 = take((size_t)nw * 4), o_q1 = take((size_t)nw * 4), o_nan = take(nan_cap * 4), o_cnt = take(64);
-    if (off > t->cond_bytes) {
-        if (t->cond_mem) { HIP_TRY(hipFree(t->cond_mem)); t->device_bytes -= (int64_t)t->cond_bytes; t->cond_mem = nullptr; t->cond_bytes = 0; }
-        const size_t want = (off + off / 4 + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1);
-        HIP_TRY(dev_malloc((void **)&t->cond_mem, want));
-        t->cond_bytes = want; t->device_bytes += (int64_t)t->cond_bytes;
-    }
+    PYDEM_TRY(tile_reserve(t, &t->cond_mem, &t->cond_bytes, off, (off + off / 4 + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1), false));
     char *base = (char *)t->cond_mem;
     t->cond_node = base + o_node; t->cond_edge = base + o_edge; t->cond_slot = (double *)(base + o_slot);
     t->cond_q0 = (int32_t *)(base + o_q0); t->cond_q1 = (int32_t *)(base + o_q1); t->cond_nanq = (int32_t *)(base + o_nan);
