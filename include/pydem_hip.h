@@ -29,6 +29,8 @@
  *                             sweep of a labelling over the tree of heaviest out-edges) -- no reference method
  *   pydem_fill_depressions    depression filling of the resident elevation (PitRemove / priority-flood + epsilon: the greatest
  *                             fixed point of a monotone recursion, by coloured LDS block relaxation) -- no reference method
+ *   pydem_fill_seam_*         the same fill across the tiles of a mosaic: a resumable relaxation per tile with caps on the lines
+ *                             that neighbouring tiles share -- no reference method
  *   pydem_depressions         the depression inventory of the resident elevation (the classic fill in scratch, a block union-find
  *                             over the raised cells, integer per-label reductions) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
@@ -198,9 +200,46 @@ int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_
  * PYDEM_FILL_MAX_PASSES passes (default 100000, read per call) did not reach the fixed point: W lives in scratch until the end,
  * so the elevation is then exactly what it was.  PYDEM_FILL_LOCAL=0 (read per call): a block visit makes one relaxation step
  * instead of iterating to its local fixed point -- the same result by another schedule, for the tests.  Per tile: a depression
- * cut by the tile's border drains off the tile. */
+ * cut by the tile's border drains off the tile (pydem_fill_seam_* below fills across tiles). */
 int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlets, double *depth, int64_t *n_raised, double *max_depth,
                            int64_t *passes, double *ms);
+/* The same fill ACROSS tiles (csrc/fill_depressions.hip): a session of four calls on a tile, driven from outside so that the tiles
+ * of a mosaic end at the fill of the whole mosaic, bit for bit (pydem_amd/process_manager.py: process_fill_depressions; the host
+ * twin is pydem_amd/conditioning.py: SeamFill).  The tiles are windows of one pixel lattice and neighbouring tiles share at least
+ * one line.  A border cell of a tile is a SEAM cell when all 8 of its lattice neighbours are held by some tile; the caller says
+ * which are.  A seam cell is not open by position (it stays open beside no data and where `outlets` marks it); every other border
+ * cell is open as in pydem_fill_depressions.  The session computes the greatest solution of
+ *     W[c] = z[c]                                                                        on open cells,
+ *     W[c] = max(z[c], min(X[c], min over the in-tile finite neighbours v of (W[v] + eps)))    elsewhere,
+ * where the cap X[c] is +inf except on seam cells, and there the smallest current W[c] of the OTHER tiles that hold c, taken as
+ * it is (no + eps; NaN counts as +inf).  The recursion is monotone in W and in X, so W at its fixed point for caps X is a valid
+ * start for any caps X' <= X: the caller exchanges lines and relaxes again until no cap falls, and every copy of a cell then
+ * holds the value of the whole-mosaic fill.  Caps may only fall.  The elevation must not be replaced while a session is open.
+ *   pydem_fill_seam_begin: seam_top / seam_bottom (m entries), seam_left / seam_right (n entries): uint8 on the host, nonzero = seam
+ *   cell, NULL = none; a corner is a seam cell if either of its lines says so.  Holds three device blocks until the end, counted
+ *   by pydem_tile_device_bytes: W (8 n m bytes), the flag words of the 32 x 32 blocks (4 ceil(n/32) ceil(m/32) bytes) and the cap
+ *   lines (8 (2 m + 2 n) bytes).  W = z on open cells, +inf elsewhere, NaN kept.  *amax: max |z| over the finite cells.  -2 for
+ *   +-inf in z and for a second begin without an end (nothing is held then).
+ *   pydem_fill_seam_relax: cap_top / cap_bottom (m), cap_left / cap_right (n): float64 on the host, NULL = unchanged; where two
+ *   lines meet at a corner the smaller value counts.  An entry above the one the session holds: -2, nothing changes.  The blocks
+ *   whose caps fell are flagged (all blocks on the first call) and the pass loop of pydem_fill_depressions runs to the fixed
+ *   point.  eps: finite, >= 0, the same in every relax of a session, not vanishing at *amax (-2).  *n_lowered: cells whose W is
+ *   lower after the call than before it (0: the tile did not move).  *passes, *ms as in pydem_fill_depressions.  Reads
+ *   PYDEM_FILL_LOCAL, PYDEM_FILL_MAX_PASSES and PYDEM_FILL_CHECK_EVERY per call; -5 at the pass bound: the session stays open (W is
+ *   still an upper bound, the caps are taken), the elevation is untouched.
+ *   pydem_fill_seam_get_lines: rows (axes[k] == 0, m doubles) and columns (axes[k] == 1, n doubles) of W at indices[k] (negative: from
+ *   the end) into dsts[k], with one synchronisation.  A neighbour that shares `overlap` lines needs line overlap - 1, not only line 0.
+ *   pydem_fill_seam_end: commit != 0: -5 while W still holds +inf (the session stays open); otherwise elev = W with depth, *n_raised,
+ *   *max_depth, the dtype rule and the invalidations of pydem_fill_depressions.  commit == 0: the elevation and everything computed
+ *   from it stay bit for bit what they were.  Either way the three blocks go back and pydem_tile_device_bytes is what it was before
+ *   begin.  pydem_tile_destroy with an open session frees it.  -2 without an open session.
+ * Limits: one pixel size, overlap >= 1, one process; the depression inventory across tiles is not computed. */
+int pydem_fill_seam_begin(pydem_tile *t, const uint8_t *outlets, const uint8_t *seam_top, const uint8_t *seam_bottom,
+                          const uint8_t *seam_left, const uint8_t *seam_right, double *amax);
+int pydem_fill_seam_relax(pydem_tile *t, double eps, const double *cap_top, const double *cap_bottom, const double *cap_left,
+                          const double *cap_right, int64_t *n_lowered, int64_t *passes, double *ms);
+int pydem_fill_seam_get_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts);
+int pydem_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_raised, double *max_depth);
 /* The depression inventory of the resident float64 elevation z (csrc/depressions.hip): which closed depressions there are, and for
  * each where it is, how large, how deep, what volume, where it spills and where its bottom lies; no reference method.
  * DEFINITION.  W is the classic fill of z: pydem_fill_depressions with eps = 0, the same open cells (border, beside no data, the

@@ -75,6 +75,10 @@ SYMBOLS = {
     'pydem_fill_flats': (C.c_int, [_P, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     'pydem_fill_depressions': (C.c_int, [_P, C.POINTER(C.c_double), _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    'pydem_fill_seam_begin': (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    'pydem_fill_seam_relax': (C.c_int, [_P, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    'pydem_fill_seam_get_lines': (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    'pydem_fill_seam_end': (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'pydem_depressions': (C.c_int, [_P, _P, C.c_double, C.c_int64, C.c_double, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P,
                                     C.POINTER(C.c_int64), _P]),
     'pydem_depressions_table': (C.c_int, [_P, C.c_int64, _P]),
@@ -301,6 +305,55 @@ class Tile(object):
         check(self.lib.pydem_fill_depressions(self._h, C.byref(eps), _ptr(mask), _ptr(depth), C.byref(raised), C.byref(dmax),
                                               C.byref(passes), C.byref(ms)))
         return depth, eps.value, int(raised.value), dmax.value, int(passes.value), ms.value
+
+    # the fill across tiles: a session on the tile (pydem_fill_seam_*); lines are keyed 'top', 'bottom', 'left', 'right'
+    SEAM_SIDES = ('top', 'bottom', 'left', 'right')
+
+    def _side_lines(self, lines, dtype, what):
+        """the four optional lines of `lines` (a dict by side, or None) as contiguous arrays of `dtype` (None: NULL)"""
+        out = []
+        for side in self.SEAM_SIDES:
+            a = None if lines is None else lines.get(side)
+            if a is not None:
+                a = np.ascontiguousarray(np.asarray(a) != 0, np.uint8) if dtype == np.uint8 else np.ascontiguousarray(a, dtype)
+                want = self.shape[1] if side in ('top', 'bottom') else self.shape[0]
+                if a.shape != (want,):
+                    raise ValueError("%s line %r of shape %r for a tile of shape %r" % (what, side, a.shape, self.shape))
+            out.append(a)
+        return out
+
+    def fill_seam_begin(self, seam=None, outlets=None):
+        """pydem_fill_seam_begin: max |z| of the resident elevation.  seam: {'top' | 'bottom' | 'left' | 'right': mask line}."""
+        mask = None if outlets is None else self._mask(outlets, 'outlets mask')
+        lines = self._side_lines(seam, np.uint8, 'seam')
+        amax = C.c_double(0)
+        check(self.lib.pydem_fill_seam_begin(self._h, _ptr(mask), *([_ptr(a) for a in lines] + [C.byref(amax)])))
+        return amax.value
+
+    def fill_seam_relax(self, eps, caps=None):
+        """pydem_fill_seam_relax: (cells that fell, passes, device ms).  caps: {side: float64 line}; a missing side is unchanged."""
+        lines = self._side_lines(caps, np.float64, 'cap')
+        low, passes, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
+        check(self.lib.pydem_fill_seam_relax(self._h, float(eps), *([_ptr(a) for a in lines] + [C.byref(low), C.byref(passes), C.byref(ms)])))
+        return int(low.value), int(passes.value), ms.value
+
+    def fill_seam_lines(self, requests):
+        """pydem_fill_seam_get_lines: [(axis, index)] -> list of float64 lines of the session's W, one synchronisation for all."""
+        k = len(requests)
+        outs = [np.empty(self.shape[1] if axis == 0 else self.shape[0], np.float64) for axis, _ in requests]
+        if k:
+            axes = (C.c_int * k)(*[int(r[0]) for r in requests])
+            idx = (C.c_int64 * k)(*[int(r[1]) for r in requests])
+            dsts = (C.c_void_p * k)(*[o.ctypes.data for o in outs])
+            check(self.lib.pydem_fill_seam_get_lines(self._h, k, axes, idx, dsts))
+        return outs
+
+    def fill_seam_end(self, commit=True, want_depth=False):
+        """pydem_fill_seam_end: (depth or None, raised cells, maximum depth); an abort (commit=False) returns (None, 0, 0.0)."""
+        depth = np.empty(self.shape, np.float64) if (want_depth and commit) else None
+        raised, dmax = C.c_int64(0), C.c_double(0)
+        check(self.lib.pydem_fill_seam_end(self._h, int(bool(commit)), _ptr(depth), C.byref(raised), C.byref(dmax)))
+        return depth, int(raised.value), dmax.value
 
     # struct pydem_depression (include/pydem_hip.h)
     DEPRESSION_ROW = np.dtype([(nm, np.int64) for nm in ('cells', 'r0', 'r1', 'c0', 'c1', 'bottom', 'pour', 'n_sills', 'open_sill')] +

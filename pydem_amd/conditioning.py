@@ -225,6 +225,140 @@ def fill_depressions(elev, epsilon=None, outlets=None):
     return W, W - z, eps
 
 
+# ---- depression filling across tiles: the host twin of the pydem_fill_seam_* session (csrc/fill_depressions.hip) ----
+SEAM_SIDES = ('top', 'bottom', 'left', 'right')
+
+
+def _side_index(side, n, m):
+    """the cells of a tile's border line as an index into an (n, m) array"""
+    return {'top': (0, slice(None)), 'bottom': (n - 1, slice(None)), 'left': (slice(None), 0), 'right': (slice(None), m - 1)}[side]
+
+
+class SeamFill(object):
+    """One tile's part of a fill across tiles, with the semantics of pydem_fill_seam_begin / _relax / _get_lines / _end
+    (include/pydem_hip.h).  `seam_lines`: {'top' | 'bottom' | 'left' | 'right': boolean line} (missing or None: none), the
+    border cells whose 8 lattice neighbours other tiles hold: they are not open by position.  W starts at z on the open cells --
+    the other border cells, cells beside no data, `outlets` -- and at +inf elsewhere; `relax(eps, caps)` lowers it to the
+    greatest solution of W = max(z, min(cap, min over the in-tile finite neighbours of (W + eps))) that lies below what it
+    holds, with a heap-ordered flood from the open cells (first call) and from the cells whose cap fell.  Caps may only fall
+    (ValueError otherwise); NaN in a cap counts as +inf.  It also serves the tiles the device does not take (fewer than three
+    rows or columns, masked arrays)."""
+
+    def __init__(self, z, outlets=None, seam_lines=None):
+        self.z, self.nan, _ = _fill_inputs("SeamFill", z, outlets)
+        n, m = self.z.shape
+        self.shape = (n, m)
+        seam = np.zeros((n, m), bool)
+        for side in SEAM_SIDES:
+            line = None if seam_lines is None else seam_lines.get(side)
+            if line is not None:
+                line = np.asarray(line).astype(bool)
+                if line.shape != np.shape(seam[_side_index(side, n, m)]):
+                    raise ValueError("SeamFill: seam line %r of shape %r for a tile of shape %r" % (side, line.shape, (n, m)))
+                seam[_side_index(side, n, m)] |= line
+        by_position = np.zeros((n, m), bool)
+        if n and m:
+            by_position[0, :] = by_position[-1, :] = True
+            by_position[:, 0] = by_position[:, -1] = True
+        # open: as in fill_depressions, except that a seam cell is not open by position
+        is_open = by_position & ~seam
+        if self.nan.any():
+            is_open |= ndimage.binary_dilation(self.nan, structure=_EIGHT)
+        if outlets is not None:
+            is_open |= np.asarray(outlets).astype(bool)
+        self.is_open = is_open & ~self.nan
+        with np.errstate(invalid='ignore'):
+            fin = np.abs(self.z[~self.nan])
+        self.amax = float(fin.max()) if fin.size else 0.0
+        self.W = np.where(self.nan, np.nan, np.inf)
+        self.W[self.is_open] = self.z[self.is_open]
+        self.cap = np.full((n, m), np.inf)
+        self.eps = None
+        self._first = True
+
+    def relax(self, eps, caps=None):
+        """Lower W to the fixed point for `caps` ({side: float64 line}; a missing side keeps its caps; at a corner the smaller of two
+        lines counts).  Returns the number of cells whose W fell."""
+        import heapq
+        eps = float(eps)
+        if not (np.isfinite(eps) and eps >= 0):
+            raise ValueError("SeamFill.relax: epsilon must be finite and >= 0 (got %r)" % (eps,))
+        if self.eps is not None and eps != self.eps:
+            raise ValueError("SeamFill.relax: epsilon %r, the session began with %r" % (eps, self.eps))
+        if eps > 0 and self.amax + eps == self.amax:
+            raise ValueError("SeamFill.relax: epsilon %r is not representable at the surface's magnitude (max |z| = %r)" % (eps, self.amax))
+        n, m = self.shape
+        lines = getattr(self, '_cap_lines', None)
+        if lines is None:
+            lines = self._cap_lines = {side: np.full(np.shape(self.cap[_side_index(side, n, m)]), np.inf) for side in SEAM_SIDES}
+        new = {}
+        for side in SEAM_SIDES:
+            line = None if caps is None else caps.get(side)
+            if line is None:
+                continue
+            line = np.array(line, np.float64)
+            if line.shape != lines[side].shape:
+                raise ValueError("SeamFill.relax: cap line %r of shape %r for a tile of shape %r" % (side, line.shape, (n, m)))
+            line[np.isnan(line)] = np.inf
+            if (line > lines[side]).any():
+                raise ValueError("SeamFill.relax: cap line %r rises above the cap the session holds; caps may only fall" % side)
+            new[side] = line
+        self.eps = eps
+        lines.update(new)
+        cap = np.full((n, m), np.inf)
+        for side in SEAM_SIDES:
+            idx = _side_index(side, n, m)
+            cap[idx] = np.minimum(cap[idx], lines[side])
+        fell = cap < self.cap
+        self.cap = cap
+        before = self.W.copy()
+        W, zl, capl = self.W.tolist(), self.z.tolist(), cap.tolist()
+        fixed = (self.is_open | self.nan).tolist()
+        heap = []
+        if self._first:
+            heap = [(W[r][c], r, c) for r, c in zip(*np.nonzero(self.is_open))]
+            self._first = False
+        for r, c in zip(*np.nonzero(fell & ~self.is_open & ~self.nan)):
+            v = capl[r][c] if capl[r][c] > zl[r][c] else zl[r][c]
+            if v < W[r][c]:
+                W[r][c] = v
+                heap.append((v, int(r), int(c)))
+        heapq.heapify(heap)
+        while heap:
+            w, r, c = heapq.heappop(heap)
+            if w > W[r][c]:
+                continue                            # (the cell fell again after this entry was pushed)
+            s = w + eps
+            for rr in (r - 1, r, r + 1):
+                if rr < 0 or rr >= n:
+                    continue
+                row_fixed, row_z, row_W, row_cap = fixed[rr], zl[rr], W[rr], capl[rr]
+                for cc in (c - 1, c, c + 1):
+                    if cc < 0 or cc >= m or row_fixed[cc]:
+                        continue
+                    v = s if s < row_cap[cc] else row_cap[cc]
+                    if not v > row_z[cc]:
+                        v = row_z[cc]
+                    if v < row_W[cc]:
+                        row_W[cc] = v
+                        heapq.heappush(heap, (v, rr, cc))
+        self.W = np.array(W, np.float64).reshape(n, m)
+        with np.errstate(invalid='ignore'):
+            return int(np.count_nonzero(self.W < before))
+
+    def lines(self, requests):
+        """[(axis, index)] -> rows (axis 0) and columns (axis 1) of W, copies"""
+        return [np.array(self.W[index, :] if axis == 0 else self.W[:, index]) for axis, index in requests]
+
+    def end(self, commit=True):
+        """commit: (W, depth) -- RuntimeError while W still holds +inf; otherwise None.  The session is over either way."""
+        if not commit:
+            return None
+        if np.isinf(self.W).any():
+            raise RuntimeError("SeamFill.end: %d cells of W are still +inf (no relaxation has reached them)" % int(np.isinf(self.W).sum()))
+        return self.W, self.W - self.z
+
+
 # ---- depression inventory (no reference method): the host twin of pydem_depressions (csrc/depressions.hip) ----
 DEPRESSION_DTYPE = np.dtype([('cells', np.int64), ('r0', np.int64), ('r1', np.int64), ('c0', np.int64), ('c1', np.int64),
                              ('spill_elev', np.float64), ('bottom_row', np.int64), ('bottom_col', np.int64), ('bottom_elev', np.float64),

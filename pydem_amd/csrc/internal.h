@@ -140,6 +140,13 @@ struct pydem_tile {
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
     void *scratch = nullptr; size_t scratch_bytes = 0;
+    // pydem_fill_seam_* (fill_depressions.hip), one session at a time: W of the open session (a plane), the flag words of its
+    // 32 x 32 blocks and its cap lines (top m, bottom m, left n, right n doubles; +inf: no cap), all three held from begin to end;
+    // the host's copy of the caps (a cap may only fall), max |z| of the session's init and the epsilon of its first relax (-1: none yet)
+    double *fs_W = nullptr; int32_t *fs_flags = nullptr; double *fs_caps = nullptr;
+    std::vector<double> fs_caps_h;
+    bool fs_open = false;
+    double fs_amax = 0.0, fs_eps = -1.0;
     std::vector<pydem_depression> depr;     // the table of the last pydem_depressions (host memory; pydem_depressions_table copies it out)
     std::vector<TileBlock> blocks;  // every device block the members above point to; device_bytes is their sum (both written by tile_mem.h only)
     int64_t device_bytes = 0;
@@ -216,6 +223,12 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
 // of the fill, the device copy of the outlets mask (null without one) and the passes it took
 struct FillRelax { double *W = nullptr; unsigned long long *ctr = nullptr; uint8_t *outlets = nullptr; int64_t passes = 0; };
 int fill_relax(pydem_tile *t, ArenaLease *lease, const char *who, double *epsilon, const uint8_t *outlets, hipEvent_t ev_start, FillRelax *out);
+// the seam session (fill_depressions.hip): the same relaxation on a W that stays with the tile between the calls, with caps on the
+// border lines that other tiles hold too; seam[4] / caps[4]: top, bottom, left, right (null entries allowed)
+int stage_fill_seam_begin(pydem_tile *t, const uint8_t *outlets, const uint8_t *const seam[4], double *amax);
+int stage_fill_seam_relax(pydem_tile *t, double eps, const double *const caps[4], int64_t *n_lowered, int64_t *passes, double *ms);
+int stage_fill_seam_get_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts);
+int stage_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_raised, double *max_depth);
 int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
                       int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms);
 int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);

@@ -505,6 +505,45 @@ int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     return 0;
 }
 
+// the fill across tiles: a session on the tile (fill_depressions.hip)
+int pydem_fill_seam_begin(pydem_tile *t, const uint8_t *outlets, const uint8_t *seam_top, const uint8_t *seam_bottom, const uint8_t *seam_left,
+                          const uint8_t *seam_right, double *amax)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_fill_seam_begin"));
+    const uint8_t *const seam[4] = {seam_top, seam_bottom, seam_left, seam_right};
+    return stage_fill_seam_begin(t, outlets, seam, amax);
+}
+
+int pydem_fill_seam_relax(pydem_tile *t, double eps, const double *cap_top, const double *cap_bottom, const double *cap_left,
+                          const double *cap_right, int64_t *n_lowered, int64_t *passes, double *ms)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    const double *const caps[4] = {cap_top, cap_bottom, cap_left, cap_right};
+    return stage_fill_seam_relax(t, eps, caps, n_lowered, passes, ms);
+}
+
+int pydem_fill_seam_get_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    return stage_fill_seam_get_lines(t, count, axes, indices, dsts);
+}
+
+int pydem_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_raised, double *max_depth)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    if (!commit) return stage_fill_seam_end(t, 0, nullptr, nullptr, nullptr);      // nothing of the tile but the session changes
+    if (t->fs_open && t->einc_ready) PYDEM_TRY(stage_edge_flush(t));   // (pending deltas of the incremental edge rounds belong to the surface as it is)
+    const int rc = stage_fill_seam_end(t, 1, depth, n_raised, max_depth);
+    if (rc == -2 || rc == -5) return rc;            // refused: the surface is what it was
+    t->edge_clean = false;
+    t->einc_ready = false;
+    t->graph_valid = false;
+    t->flats_state = 0;
+    for (int f = PYDEM_MAG; f < PYDEM_FIELD_COUNT; f++) t->have[f] = false;     // as after pydem_fill_depressions
+    return rc;
+}
+
 int pydem_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
                       int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms)
 {

@@ -472,6 +472,99 @@ class DEMProcessor(FlowAnalyses):
         self.fill_depressions_stats = stats
         return stats
 
+    # ---- the fill across tiles: this tile's session (include/pydem_hip.h: pydem_fill_seam_*; no counterpart in the reference).
+    # ProcessManager.process_fill_depressions drives it: begin on every tile, rounds of line exchange and relax, end.
+    _seam_host = None             # the host twin serving the open session (conditioning.SeamFill), where the device does not take the tile
+    _seam_open = False
+
+    def fill_seam_begin(self, seam, outlets=None):
+        """Open the session.  seam: {'top' | 'bottom' | 'left' | 'right': boolean line} -- the border cells whose 8 neighbours in the
+        mosaic's pixel lattice other tiles hold; they are not open by position.  outlets as in calc_fill_depressions.  Returns
+        max |z| over the finite cells."""
+        if self._seam_open:
+            raise RuntimeError("fill_seam_begin: a session is open on this tile (fill_seam_end first)")
+        mask = None if outlets is None else self._outlets_mask(outlets)
+        from . import conditioning
+        elev = self._host.get('elev')
+        on_host = False
+        self._seam_dtype = None
+        if elev is not None:
+            on_host = np.ma.isMaskedArray(elev) or np.asarray(elev).dtype.kind not in 'iuf' or np.asarray(elev).ndim != 2
+            if not on_host:
+                self._seam_dtype = np.asarray(elev).dtype
+        if min(self.shape) < 3:
+            on_host = True
+        if on_host:
+            self._seam_host = conditioning.SeamFill(self.elev, mask, seam)
+            amax = self._seam_host.amax
+        else:
+            self._ensure_tile()
+            self._push('elev')
+            amax = self._tile.fill_seam_begin(seam, mask)
+        self._seam_open = True
+        self._seam_stats = dict(epsilon=None, passes=0, ms=0.0)
+        return amax
+
+    def _seam_check(self, what):
+        if not self._seam_open:
+            raise RuntimeError("%s: no session is open on this tile (fill_seam_begin first)" % what)
+
+    def fill_seam_relax(self, eps, caps=None):
+        """Relax to the fixed point for `caps` ({side: float64 line}; a missing side keeps its caps; caps may only fall):
+        {'n_lowered', 'passes', 'ms'} (passes and ms are 0 where the host twin serves the session)."""
+        self._seam_check('fill_seam_relax')
+        if self._seam_host is not None:
+            out = dict(n_lowered=self._seam_host.relax(eps, caps), passes=0, ms=0.0)
+        else:
+            low, passes, ms = self._tile.fill_seam_relax(eps, caps)
+            out = dict(n_lowered=low, passes=passes, ms=ms)
+        st = self._seam_stats
+        st['epsilon'] = float(eps)
+        st['passes'] += out['passes']
+        st['ms'] += out['ms']
+        return out
+
+    def fill_seam_lines(self, requests):
+        """[(axis, index)] -> rows (axis 0) and columns (axis 1) of the session's W, with one synchronisation"""
+        self._seam_check('fill_seam_lines')
+        if self._seam_host is not None:
+            return self._seam_host.lines(requests)
+        return self._tile.fill_seam_lines(requests)
+
+    def fill_seam_end(self, commit=True, return_depth=False):
+        """Close the session.  commit: the elevation becomes W, with the dtype rule, the stale fields and `fill_depressions_stats`
+        of run_fill_depressions (passes and ms summed over the session's relax calls); returns the stats.  commit=False: nothing
+        of the tile changes; returns None."""
+        self._seam_check('fill_seam_end')
+        host, dtype, st = self._seam_host, self._seam_dtype, self._seam_stats
+        if not commit:
+            if host is None:
+                self._tile.fill_seam_end(False)
+            self._seam_host, self._seam_open = None, False
+            return None
+        eps = st['epsilon']
+        if host is not None:
+            W, depth = host.end(True)           # (RuntimeError while W holds +inf: the session stays open)
+            with np.errstate(invalid='ignore'):
+                raised = depth > 0
+            stats = dict(epsilon=eps, n_raised=int(raised.sum()), max_depth=float(depth[raised].max()) if raised.any() else 0.0, passes=0, ms=0.0)
+            if not eps and dtype is not None:
+                W = W.astype(dtype)
+            self.elev = W
+        else:
+            depth, n_raised, max_depth = self._tile.fill_seam_end(True, return_depth)       # (-5 while W holds +inf: the session stays open)
+            stats = dict(epsilon=eps, n_raised=n_raised, max_depth=max_depth, passes=st['passes'], ms=st['ms'])
+            self._produced('elev')
+            if not eps and dtype is not None and dtype != np.float64:
+                self.elev = self.elev.astype(dtype)             # every value of the classic fill is a value of the input
+        self._seam_host, self._seam_open = None, False
+        for nm in ('mag', 'direction', 'flats', 'uca', 'section', 'proportion', 'edge_todo', 'edge_done'):
+            self._on_device.discard(nm)             # the fields of the surface as it was
+            self._host.pop(nm, None)
+        self.fill_depth = depth if return_depth else None
+        self.fill_depressions_stats = stats
+        return stats
+
     depressions = None            # {'label', 'table'} of the last calc_depressions (no counterpart in the reference)
     depressions_stats = None      # {'n_found', 'quanta', 'passes', 'ms'} of the last calc_depressions
     kept_sinks = None             # (N, 2) int array: the outlets calc_fill_depressions_limited added

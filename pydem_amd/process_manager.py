@@ -489,6 +489,177 @@ class ProcessManager(object):
         self._per_tile(one)
         return [1] * self.n_inputs
 
+    # ------------------------------------------------------------------ depression filling across tiles
+    # The tiles are windows of one pixel lattice.  A border cell whose 8 lattice neighbours are all held by some tile is a SEAM
+    # cell: it is not open by position, and its value is capped by the other tiles' copies of it.  Every tile relaxes to its own
+    # fixed point under its caps (DEMProcessor.fill_seam_*); W and the caps only fall, and when no cap falls any more every copy
+    # of a cell holds the fill of the whole mosaic, bit for bit ("Depression filling across tiles").
+    fill_depressions = False             # process_twi fills the depressions of the mosaic between the elevation and the aspect / slope phase
+    fill_depressions_epsilon = None      # ... with this epsilon (None: automatic, from max |z| of the mosaic)
+    fill_rounds = 0                      # rounds of the last process_fill_depressions
+    fill_round_log = None                # ... and what each of them did (tools/fill_mosaic_cost.py)
+
+    def fill_lattice(self):
+        """The tiles as windows of one global pixel lattice, from the bounds alone: an (n_tiles, 4) int array of r0, c0 (the
+        window's first row and column: round((max top - top) / |dlat|) and round((left - min left) / dlon)), rows and columns.
+        NotImplementedError for tiles of more than one pixel size (a tile's far edge would move by more than the coordinate
+        rounding of compute_grid) and for offsets that are not integers to within 0.01 of a pixel."""
+        I = self._i
+        idx = self.index
+        tol = 0.5 * 10.0 ** -self.grid_round_decimals       # the coordinate rounding compute_grid works with
+        out = np.zeros((self.n_inputs, 4), np.int64)
+        out[:, 2] = np.round(idx[:, I('nrows')]).astype(np.int64)
+        out[:, 3] = np.round(idx[:, I('ncols')]).astype(np.int64)
+        for name, size, col in (('dlon', 'ncols', 1), ('dlat', 'nrows', 0)):
+            d = np.abs(idx[:, I(name)])
+            if not (np.isfinite(d).all() and (d > 0).all()) or (np.abs(d - d[0]) * idx[:, I(size)] > tol).any():
+                raise NotImplementedError("process_fill_depressions: the tiles differ in pixel size (%s from %r to %r); one pixel lattice is needed"
+                                          % (name, float(d.min()), float(d.max())))
+            edge = idx[:, I('left')] if col == 1 else -idx[:, I('top')]
+            off = (edge - edge.min()) / d[0]
+            if (np.abs(off - np.round(off)) > 0.01).any():
+                raise NotImplementedError("process_fill_depressions: tile %d does not lie on the pixel lattice of the mosaic (offset %r pixels)"
+                                          % (int(np.argmax(np.abs(off - np.round(off)))), float(off[np.argmax(np.abs(off - np.round(off)))])))
+            out[:, col] = np.round(off).astype(np.int64)
+        return out
+
+    @staticmethod
+    def _fill_seams(lat):
+        """Per tile {side: boolean seam line}, and the links of the line exchange: per tile a list of (side, slice into that line,
+        other tile, axis, local index in the other tile, slice into the other tile's line) -- every other tile's copy of a part of
+        the side.  NotImplementedError when two 8-adjacent covered cells, at least one of them closed by position, share no tile
+        (abutting tiles: overlap 0)."""
+        nt = lat.shape[0]
+        r0, c0 = lat[:, 0], lat[:, 1]
+        r1, c1 = r0 + lat[:, 2], c0 + lat[:, 3]
+        seams, links = [], []
+        for i in range(nt):
+            seam_i, links_i = {}, []
+            for side in SIDES:
+                rows = side in ('top', 'bottom')
+                # x: the coordinate across the line, a: along it; the line is x0, its outer neighbour x0 + d
+                x0 = {'top': r0[i], 'bottom': r1[i] - 1, 'left': c0[i], 'right': c1[i] - 1}[side]
+                d = -1 if side in ('top', 'left') else 1
+                a0, a1 = (c0[i], c1[i]) if rows else (r0[i], r1[i])
+                xs0, xs1, as0, as1 = (r0, r1, c0, c1) if rows else (c0, c1, r0, r1)
+                L = int(a1 - a0)
+                cov = np.zeros((4, L + 4), bool)            # the lines x0 - d (inner), x0, x0 + d (outer), x0 + 2 d over a0 - 2 .. a1 + 1
+                pair = np.zeros((3, L), bool)               # t = -1, 0, 1: some tile holds (x0, a) and (x0 + d, a + t)
+                for j in range(nt):
+                    lo, hi = max(as0[j], a0 - 2), min(as1[j], a1 + 2)
+                    if lo >= hi:
+                        continue
+                    for k, x in enumerate((x0 - d, x0, x0 + d, x0 + 2 * d)):
+                        if xs0[j] <= x < xs1[j]:
+                            cov[k, lo - (a0 - 2):hi - (a0 - 2)] = True
+                    if xs0[j] <= x0 < xs1[j] and xs0[j] <= x0 + d < xs1[j]:
+                        for t in (-1, 0, 1):
+                            lo_t, hi_t = max(as0[j], as0[j] - t, a0), min(as1[j], as1[j] - t, a1)
+                            if lo_t < hi_t:
+                                pair[t + 1, lo_t - a0:hi_t - a0] = True
+                    if j != i and xs0[j] <= x0 < xs1[j]:
+                        lo_c, hi_c = max(as0[j], a0), min(as1[j], a1)
+                        if lo_c < hi_c:
+                            links_i.append((side, slice(int(lo_c - a0), int(hi_c - a0)), j, 0 if rows else 1, int(x0 - xs0[j]),
+                                            slice(int(lo_c - as0[j]), int(hi_c - as0[j]))))
+                # closed by position: the 3 x 3 neighbourhood is covered -- of the line's cells (the seam cells) and of the outer line's
+                # cells at a0 - 1 .. a1; a cell with an uncovered neighbour is open, and two open cells need not meet in a tile
+                def closed(k):
+                    full = cov[k - 1:k + 2].all(axis=0)
+                    return full[0:L + 2] & full[1:L + 3] & full[2:L + 4]
+                seam_i[side] = closed(1)[1:L + 1]
+                outer_closed = closed(2)
+                for t in (-1, 0, 1):
+                    if (cov[2, 2 + t:2 + t + L] & ~pair[t + 1] & (seam_i[side] | outer_closed[1 + t:1 + t + L])).any():
+                        raise NotImplementedError("process_fill_depressions: tile %d and a neighbour at its %s side share no line (overlap 0); "
+                                                  "neighbouring tiles must overlap by at least one pixel" % (i, side))
+            seams.append(seam_i)
+            links.append(links_i)
+        return seams, links
+
+    def process_fill_depressions(self, epsilon=None, outlets=None, max_rounds=10000):
+        """Fill the depressions of the MOSAIC (calc_fill_depressions fills a tile and lets a depression that the tile's border cuts
+        drain off the tile): afterwards every tile holds its window of conditioning.fill_depressions of the stitched raster, bit
+        for bit, overlap cells included.  epsilon: None is automatic, from the largest max |z| of the tiles.  outlets: lattice
+        (row, col) pairs (rows and columns of `fill_lattice`), each marked in every tile that holds the cell.  Jacobi rounds:
+        one snapshot of the lines the tiles share, the caps from it, then every tile whose caps fell relaxes (all tiles in the
+        first round); it ends when no cap fell (`fill_rounds`).  After `max_rounds` rounds, or on any error, every session is
+        aborted and the error raised: no elevation has changed.  Needs one pixel size, overlap >= 1 and all tiles in this
+        process (NotImplementedError before any tile is touched)."""
+        from . import conditioning
+        lat = self.fill_lattice()
+        seams, links = self._fill_seams(lat)
+        owned = list(self._owned())
+        if len(owned) != self.n_inputs:
+            raise NotImplementedError("process_fill_depressions: every tile must belong to this process (multi-rank runs are not supported)")
+        if epsilon is not None:
+            epsilon = conditioning.fill_depressions_epsilon(np.zeros(1), epsilon)       # (type and range; the magnitude below)
+        per_tile_outlets = [None] * self.n_inputs
+        if outlets is not None:
+            cells = np.asarray(outlets, np.int64).reshape(-1, 2)
+            for i in owned:
+                rr, cc = cells[:, 0] - lat[i, 0], cells[:, 1] - lat[i, 1]
+                ok = (rr >= 0) & (rr < lat[i, 2]) & (cc >= 0) & (cc < lat[i, 3])
+                if ok.any():
+                    per_tile_outlets[i] = np.stack([rr[ok], cc[ok]], axis=1)
+        if all(self.tiles[i] is None for i in owned):
+            self.process_elevation()
+        begun = []
+        try:
+            amax = 0.0
+            for i in owned:
+                amax = max(amax, float(self.tiles[i].fill_seam_begin(seams[i], per_tile_outlets[i])))
+                begun.append(i)
+            eps = conditioning.fill_depressions_epsilon(np.array([amax]), epsilon)
+            # the lines of W that other tiles read, per tile
+            wanted = {j: sorted(set((lk[3], lk[4]) for i in owned for lk in links[i] if lk[2] == j)) for j in owned}
+            caps = {i: {side: np.full(seams[i][side].shape, np.inf) for side in SIDES} for i in owned}
+            rounds = 0
+            log = self.fill_round_log = []          # per round: tiles relaxed, cells that fell, passes, device ms (summed over the tiles), wall ms
+            while True:
+                snap = {}
+                for j in owned:
+                    if wanted[j]:
+                        snap.update({(j,) + key: line for key, line in zip(wanted[j], self.tiles[j].fill_seam_lines(wanted[j]))})
+                todo = {}
+                for i in owned:
+                    new = {side: np.full(seams[i][side].shape, np.inf) for side in SIDES}
+                    for side, mine, j, axis, index, theirs in links[i]:
+                        seg = snap[(j, axis, index)][theirs]
+                        new[side][mine] = np.fmin(new[side][mine], np.where(np.isnan(seg), np.inf, seg))
+                    fell = False
+                    for side in SIDES:
+                        new[side][~seams[i][side]] = np.inf             # (only a seam cell is capped)
+                        fell = fell or bool((new[side] < caps[i][side]).any())
+                    if fell or rounds == 0:
+                        todo[i] = new
+                if not todo:
+                    break
+                if rounds >= max_rounds:
+                    raise RuntimeError("process_fill_depressions: caps still fall after %d rounds (max_rounds)" % rounds)
+                caps.update(todo)
+                got = {}
+                t0 = time.perf_counter()
+                self._per_tile(lambda i: got.__setitem__(i, self.tiles[i].fill_seam_relax(eps, todo[i])) if i in todo else None)
+                log.append(dict(tiles=len(todo), n_lowered=sum(g['n_lowered'] for g in got.values()), passes=sum(g['passes'] for g in got.values()),
+                                device_ms=sum(g['ms'] for g in got.values()), wall_ms=(time.perf_counter() - t0) * 1e3))
+                rounds += 1
+            for i in owned:
+                self.tiles[i].fill_seam_end(True)
+                begun.remove(i)
+                if self.checkpoint:
+                    self._store(i, 'elev', {'elev': np.asarray(self.tiles[i].elev, float)})
+        except BaseException:
+            for i in begun:
+                try:
+                    self.tiles[i].fill_seam_end(False)
+                except Exception:
+                    logger.exception("process_fill_depressions: could not abort the session of tile %d", i)
+            raise
+        self.fill_rounds = rounds
+        self.fill_depressions_epsilon_used = eps
+        return [1] * self.n_inputs
+
     def _patch_overlap1_edges(self):
         """Single-pixel-overlap fix of the reference's calc_uca worker (:102-180): an edge cell whose
         flow leaves the tile takes aspect/slope from the coincident (or adjacent) neighbour line.  The
@@ -1258,6 +1429,9 @@ class ProcessManager(object):
         self.compute_grid()
         logger.info("Compute Elevation")
         self.process_elevation()
+        if self.fill_depressions:
+            logger.info("Fill Depressions")
+            self.process_fill_depressions(self.fill_depressions_epsilon)
         logger.info("Compute Aspect and Slope")
         self.process_aspect_slope()
         logger.info("Compute UCA")
