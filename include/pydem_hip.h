@@ -30,7 +30,8 @@
  *   pydem_fill_depressions    depression filling of the resident elevation (PitRemove / priority-flood + epsilon: the greatest
  *                             fixed point of a monotone recursion, by coloured LDS block relaxation) -- no reference method
  *   pydem_fill_seam_*         the same fill across the tiles of a mosaic: a resumable relaxation per tile with caps on the lines
- *                             that neighbouring tiles share -- no reference method
+ *                             that neighbouring tiles share; and, on the W it ends with, the tile's part of the depression
+ *                             inventory of the mosaic (_label, _label_roots, _get_id_lines, _inventory, _labels) -- no reference method
  *   pydem_depressions         the depression inventory of the resident elevation (the classic fill in scratch, a block union-find
  *                             over the raised cells, integer per-label reductions) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
@@ -233,13 +234,47 @@ int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
  *   *max_depth, the dtype rule and the invalidations of pydem_fill_depressions.  commit == 0: the elevation and everything computed
  *   from it stay bit for bit what they were.  Either way the three blocks go back and pydem_tile_device_bytes is what it was before
  *   begin.  pydem_tile_destroy with an open session frees it.  -2 without an open session.
- * Limits: one pixel size, overlap >= 1, one process; the depression inventory across tiles is not computed. */
+ * THE INVENTORY ACROSS TILES (csrc/depressions.hip; pydem_amd/process_manager.py: process_depressions; host twin: SeamFill.label /
+ * id_lines / inventory / labels).  Once no cap falls at eps = 0 the session's W is the tile's window of the whole-mosaic classic
+ * fill, and five more calls of the session give the tile's part of pydem_depressions of the whole mosaic.  They read z and W and
+ * change nothing of the tile; the session is then ended with commit == 0.
+ *   pydem_fill_seam_label: the 8-connected components of W > z INSIDE the tile, numbered 1 .. *n_local in ascending order of their
+ *   smallest linear index r*m + c, with the union-find of pydem_depressions (PYDEM_DEPR_LOCAL as there).  The plane of local ids
+ *   (int32: 0 not raised, -1 no data) stays on the device as a fourth session block of 4 n m bytes, counted by
+ *   pydem_tile_device_bytes from this call until pydem_fill_seam_end.  *max_depth: the largest W - z of the tile.  -5 while W holds
+ *   +inf.  *ms: device-clock time of the call (also in _inventory and _labels).
+ *   pydem_fill_seam_label_roots: roots[k], levels[k] (count == *n_local entries): the smallest linear index of local component
+ *   k + 1, and its level W there.
+ *   pydem_fill_seam_get_id_lines: as pydem_fill_seam_get_lines, for rows and columns of the id plane (int32).
+ *   pydem_fill_seam_inventory: the tile's PARTIAL TABLE.  The caller has joined the local components of all tiles into the
+ *   mosaic's depressions and numbered those this tile can meet 1 .. n_rows.  lut (int32, *n_local + 1 entries, lut[0] unused):
+ *   local id -> row.  owner (uint8 [n,m]): nonzero where this tile is the one that counts the lattice cell; every lattice cell has
+ *   one owner.  halo_ids, halo_W (2 m + 2 n + 4 entries): the ring just outside the window -- the row above over columns -1 .. m,
+ *   the row below over the same columns, the column left over rows 0 .. n-1, the column right -- as the row of the depression the
+ *   cell lies in (0: finite and not raised, -1: no data or held by no tile) and its W.  row_area (n doubles), shift_area,
+ *   shift_volume: the terms and the fixed-point shifts of area and volume (a cell adds llrint(ldexp(p, shift)), as in
+ *   pydem_depressions; the caller derives the shifts from the whole mosaic).  outlets as in pydem_fill_seam_begin, may be NULL.
+ *   table: 13 columns of n_rows uint64 words, column-major: cells, r0, r1, c0, c1 (local, over the owned raised cells of the row),
+ *   the order-preserving pattern of their lowest z, the smallest local index among the owned cells at that z, the smallest local
+ *   index among the owned sill cells, their number, 1 when one of them is open, the two fixed-point sums, the bits of z at the
+ *   bottom cell.  An owned finite cell that is not raised is a sill cell of every row whose level equals its z among its 8
+ *   neighbours, in the window or in the halo, once per row; it is open when a neighbour is -1 or `outlets` marks it.  A row
+ *   without owned cells keeps ~0 in the minimum columns and 0 elsewhere.  -2 for a lookup or halo entry outside 0 (-1) .. n_rows.
+ *   pydem_fill_seam_labels: label (int32 [n,m] on the host) = lut[local id] on raised cells, 0 and -1 as in the id plane.
+ * Limits: one pixel size, overlap >= 1, one process. */
 int pydem_fill_seam_begin(pydem_tile *t, const uint8_t *outlets, const uint8_t *seam_top, const uint8_t *seam_bottom,
                           const uint8_t *seam_left, const uint8_t *seam_right, double *amax);
 int pydem_fill_seam_relax(pydem_tile *t, double eps, const double *cap_top, const double *cap_bottom, const double *cap_left,
                           const double *cap_right, int64_t *n_lowered, int64_t *passes, double *ms);
 int pydem_fill_seam_get_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts);
 int pydem_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_raised, double *max_depth);
+int pydem_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, double *ms);
+int pydem_fill_seam_label_roots(pydem_tile *t, int64_t count, int32_t *roots, double *levels);
+int pydem_fill_seam_get_id_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts);
+int pydem_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t n_rows, const uint8_t *owner, const uint8_t *outlets,
+                              const int32_t *halo_ids, const double *halo_W, const double *row_area, int shift_area, int shift_volume,
+                              uint64_t *table, double *ms);
+int pydem_fill_seam_labels(pydem_tile *t, const int32_t *lut, int32_t *label, double *ms);
 /* The depression inventory of the resident float64 elevation z (csrc/depressions.hip): which closed depressions there are, and for
  * each where it is, how large, how deep, what volume, where it spills and where its bottom lies; no reference method.
  * DEFINITION.  W is the classic fill of z: pydem_fill_depressions with eps = 0, the same open cells (border, beside no data, the

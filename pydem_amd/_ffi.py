@@ -79,6 +79,11 @@ SYMBOLS = {
     'pydem_fill_seam_relax': (C.c_int, [_P, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'pydem_fill_seam_get_lines': (C.c_int, [_P, C.c_int, _P, _P, _P]),
     'pydem_fill_seam_end': (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    'pydem_fill_seam_label': (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'pydem_fill_seam_label_roots': (C.c_int, [_P, C.c_int64, _P, _P]),
+    'pydem_fill_seam_get_id_lines': (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    'pydem_fill_seam_inventory': (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_double)]),
+    'pydem_fill_seam_labels': (C.c_int, [_P, _P, _P, C.POINTER(C.c_double)]),
     'pydem_depressions': (C.c_int, [_P, _P, C.c_double, C.c_int64, C.c_double, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P,
                                     C.POINTER(C.c_int64), _P]),
     'pydem_depressions_table': (C.c_int, [_P, C.c_int64, _P]),
@@ -354,6 +359,66 @@ class Tile(object):
         raised, dmax = C.c_int64(0), C.c_double(0)
         check(self.lib.pydem_fill_seam_end(self._h, int(bool(commit)), _ptr(depth), C.byref(raised), C.byref(dmax)))
         return depth, int(raised.value), dmax.value
+
+    # the session's inventory part (pydem_fill_seam_label ...): the tile's share of the depression inventory of the mosaic
+    _seam_n_local = -1            # local ids of the last fill_seam_label (the library reads that many lookup entries, and entry 0)
+
+    def fill_seam_label(self):
+        """pydem_fill_seam_label + _label_roots: (roots, levels, largest depth, device ms) -- the first cell (int32 linear index) and
+        the level of each local component of W > z, in the order of their local ids 1 .. len(roots)."""
+        k, dmax, ms = C.c_int64(0), C.c_double(0), C.c_double(0)
+        check(self.lib.pydem_fill_seam_label(self._h, C.byref(k), C.byref(dmax), C.byref(ms)))
+        roots, levels = np.empty(k.value, np.int32), np.empty(k.value, np.float64)
+        check(self.lib.pydem_fill_seam_label_roots(self._h, k.value, _ptr(roots), _ptr(levels)))
+        self._seam_n_local = int(k.value)
+        return roots, levels, dmax.value, ms.value
+
+    def fill_seam_id_lines(self, requests):
+        """pydem_fill_seam_get_id_lines: [(axis, index)] -> list of int32 lines of the session's id plane, one synchronisation for all."""
+        k = len(requests)
+        outs = [np.empty(self.shape[1] if axis == 0 else self.shape[0], np.int32) for axis, _ in requests]
+        if k:
+            axes = (C.c_int * k)(*[int(r[0]) for r in requests])
+            idx = (C.c_int64 * k)(*[int(r[1]) for r in requests])
+            dsts = (C.c_void_p * k)(*[o.ctypes.data for o in outs])
+            check(self.lib.pydem_fill_seam_get_id_lines(self._h, k, axes, idx, dsts))
+        return outs
+
+    def fill_seam_inventory(self, lut, n_rows, owner, halo_ids, halo_W, row_area, shift_area, shift_volume, outlets=None):
+        """pydem_fill_seam_inventory: (partial table, uint64 [13, n_rows]; device ms).  The shapes are checked here, the values by
+        the library."""
+        n, m = self.shape
+        lut = np.ascontiguousarray(lut, np.int32)
+        owner = self._mask(owner, 'owner plane')
+        mask = None if outlets is None else self._mask(outlets, 'outlets mask')
+        halo_ids = np.ascontiguousarray(halo_ids, np.int32)
+        halo_W = np.ascontiguousarray(halo_W, np.float64)
+        row_area = np.ascontiguousarray(row_area, np.float64)
+        ring = 2 * m + 2 * n + 4
+        if halo_ids.shape != (ring,) or halo_W.shape != (ring,) or row_area.shape != (n,) or lut.ndim != 1:
+            raise ValueError("fill_seam_inventory: halo of %r / %r entries (%d wanted), row_area of shape %r for a tile of shape %r"
+                             % (halo_ids.shape, halo_W.shape, ring, row_area.shape, self.shape))
+        table = np.zeros((13, int(n_rows)), np.uint64)
+        ms = C.c_double(0)
+        # (the library reads n_local + 1 lookup entries: the length is checked against the labels it holds)
+        self._seam_lut_check(lut)
+        check(self.lib.pydem_fill_seam_inventory(self._h, _ptr(lut), int(n_rows), _ptr(owner), _ptr(mask), _ptr(halo_ids), _ptr(halo_W),
+                                                 _ptr(row_area), int(shift_area), int(shift_volume), _ptr(table), C.byref(ms)))
+        return table, ms.value
+
+    def _seam_lut_check(self, lut):
+        """ValueError unless `lut` has one entry per local id of the session's labels, plus entry 0"""
+        if lut.shape != (self._seam_n_local + 1,):
+            raise ValueError("fill_seam: a lookup of shape %r for %d local ids (one entry each, and entry 0)" % (lut.shape, self._seam_n_local))
+
+    def fill_seam_labels(self, lut):
+        """pydem_fill_seam_labels: (int32 label plane, device ms); lut: local id -> label, entry 0 unused."""
+        lut = np.ascontiguousarray(lut, np.int32)
+        self._seam_lut_check(lut)
+        label = np.empty(self.shape, np.int32)
+        ms = C.c_double(0)
+        check(self.lib.pydem_fill_seam_labels(self._h, _ptr(lut), _ptr(label), C.byref(ms)))
+        return label, ms.value
 
     # struct pydem_depression (include/pydem_hip.h)
     DEPRESSION_ROW = np.dtype([(nm, np.int64) for nm in ('cells', 'r0', 'r1', 'c0', 'c1', 'bottom', 'pour', 'n_sills', 'open_sill')] +

@@ -267,6 +267,7 @@ class SeamFill(object):
         if outlets is not None:
             is_open |= np.asarray(outlets).astype(bool)
         self.is_open = is_open & ~self.nan
+        self.outlets = None if outlets is None else np.asarray(outlets).astype(bool)
         with np.errstate(invalid='ignore'):
             fin = np.abs(self.z[~self.nan])
         self.amax = float(fin.max()) if fin.size else 0.0
@@ -357,6 +358,110 @@ class SeamFill(object):
         if np.isinf(self.W).any():
             raise RuntimeError("SeamFill.end: %d cells of W are still +inf (no relaxation has reached them)" % int(np.isinf(self.W).sum()))
         return self.W, self.W - self.z
+
+    # ---- the inventory across tiles: the twin of pydem_fill_seam_label / _get_id_lines / _inventory / _labels (include/pydem_hip.h)
+    ids = None                    # the plane of local ids after label()
+
+    def label(self):
+        """The 8-connected components of W > z inside the tile, numbered in ascending order of their first cell: (roots, levels,
+        largest depth) -- the first cell (int32 linear index) and the level of each.  RuntimeError while W holds +inf."""
+        if np.isinf(self.W).any():
+            raise RuntimeError("SeamFill.label: cells of W are still +inf (no relaxation has reached them)")
+        with np.errstate(invalid='ignore'):
+            raised = self.W > self.z
+        lab, K = ndimage.label(raised, structure=_EIGHT)
+        self.ids = np.where(self.nan, -1, lab).astype(np.int32)
+        idx = np.flatnonzero(raised)
+        roots = np.zeros(K, np.int32)
+        roots[lab.ravel()[idx[::-1]] - 1] = idx[::-1]               # (the last store of a label is its smallest index)
+        depth = self.W.ravel()[idx] - self.z.ravel()[idx]
+        return roots, self.W.ravel()[roots], float(depth.max()) if K else 0.0
+
+    def _labelled(self, what):
+        if self.ids is None:
+            raise RuntimeError("SeamFill.%s: the session has no labels (label first)" % what)
+
+    def id_lines(self, requests):
+        """[(axis, index)] -> rows (axis 0) and columns (axis 1) of the id plane, copies"""
+        self._labelled('id_lines')
+        return [np.array(self.ids[index, :] if axis == 0 else self.ids[:, index]) for axis, index in requests]
+
+    def inventory(self, lut, n_rows, owner, halo_ids, halo_W, row_area, shift_area, shift_volume):
+        """The tile's partial table over the cells `owner` marks: uint64 [len(SEAM_TABLE_COLS), n_rows], word for word what
+        pydem_fill_seam_inventory returns (include/pydem_hip.h has every argument and column).  The outlets are those of the
+        session."""
+        self._labelled('inventory')
+        n, m = self.shape
+        NN, T = n * m, int(n_rows)
+        lut = np.asarray(lut, np.int64)
+        halo_ids, halo_W = np.asarray(halo_ids, np.int64), np.asarray(halo_W, np.float64)
+        if lut.shape != (int(self.ids.max(initial=0)) + 1,) or halo_ids.shape != (2 * m + 2 * n + 4,) or halo_W.shape != halo_ids.shape:
+            raise ValueError("SeamFill.inventory: lookup of shape %r, halo of shape %r for a tile of shape %r" % (lut.shape, halo_ids.shape, (n, m)))
+        if lut.min(initial=0) < 0 or lut.max(initial=0) > T or halo_ids.min() < -1 or halo_ids.max() > T:
+            raise ValueError("SeamFill.inventory: a lookup or halo entry outside 0 (-1) .. %d" % T)
+        col = {nm: k for k, nm in enumerate(SEAM_TABLE_COLS)}
+        tab = np.zeros((len(SEAM_TABLE_COLS), T), np.uint64)
+        for nm in ('r0', 'c0', 'zmin', 'bottom', 'pour'):
+            tab[col[nm]] = ~np.uint64(0)
+        if T == 0:
+            return tab
+        owner = np.asarray(owner).astype(bool)
+        ra = np.ascontiguousarray(row_area, np.float64)
+        z, W = self.z, self.W
+        g = np.where(self.ids > 0, lut[np.maximum(self.ids, 0)], np.where(self.ids < 0, -1, 0))        # rows, 0, -1 per cell
+        idx = np.flatnonzero(owner & (g > 0))
+        k = g.ravel()[idx] - 1
+        r, c = idx // m, idx % m
+        zc = z.ravel()[idx]
+        key = (zc + 0.0).view(np.uint64)
+        key = np.where(key >> np.uint64(63), ~key, key | np.uint64(1 << 63))
+        tab[col['cells']] = np.bincount(k, minlength=T).astype(np.uint64)
+        for nm, v, op in (('r0', r, np.minimum), ('r1', r, np.maximum), ('c0', c, np.minimum), ('c1', c, np.maximum), ('zmin', key, np.minimum)):
+            op.at(tab[col[nm]], k, v.astype(np.uint64))
+        low = key == tab[col['zmin']][k]
+        np.minimum.at(tab[col['bottom']], k[low], idx[low].astype(np.uint64))
+        has = tab[col['bottom']] < NN
+        tab[col['bottom_elev']][has] = z.ravel()[tab[col['bottom']][has].astype(np.int64)].view(np.uint64)
+        depth = W.ravel()[idx] - zc
+        for nm, terms in (('area', np.ldexp(ra[r], int(shift_area))), ('volume', np.ldexp(depth * ra[r], int(shift_volume)))):
+            s = np.zeros(T, np.int64)
+            np.add.at(s, k, np.rint(terms).astype(np.int64))
+            tab[col[nm]] = s.view(np.uint64)
+        # sills, on the window with its halo ring
+        gp = np.zeros((n + 2, m + 2), np.int64)
+        Wp = np.zeros((n + 2, m + 2))
+        gp[1:-1, 1:-1], Wp[1:-1, 1:-1] = g, W
+        for plane, halo in ((gp, halo_ids), (Wp, halo_W)):
+            plane[0, :], plane[-1, :] = halo[:m + 2], halo[m + 2:2 * m + 4]
+            plane[1:-1, 0], plane[1:-1, -1] = halo[2 * m + 4:2 * m + 4 + n], halo[2 * m + 4 + n:]
+        cand = owner & (self.ids == 0)
+        is_open = np.zeros((n, m), bool) if self.outlets is None else self.outlets.copy()
+        pairs = []
+        for dr in (0, 1, 2):
+            for dc in (0, 1, 2):
+                if dr == 1 and dc == 1:
+                    continue
+                nl = gp[dr:dr + n, dc:dc + m]
+                is_open |= nl < 0
+                with np.errstate(invalid='ignore'):
+                    cell = np.flatnonzero(cand & (nl > 0) & (Wp[dr:dr + n, dc:dc + m] == z))
+                pairs.append((nl.ravel()[cell] - 1) * NN + cell)
+        pairs = np.unique(np.concatenate(pairs))
+        sl, sc = pairs // NN, pairs % NN
+        tab[col['n_sills']] = np.bincount(sl, minlength=T).astype(np.uint64)
+        np.minimum.at(tab[col['pour']], sl, sc.astype(np.uint64))
+        np.maximum.at(tab[col['open']], sl, is_open.ravel()[sc].astype(np.uint64))
+        return tab
+
+    def labels(self, lut):
+        """the label plane: lut[local id] on raised cells, 0 and -1 as in the id plane"""
+        self._labelled('labels')
+        lut = np.asarray(lut, np.int32)
+        return np.where(self.ids > 0, lut[np.maximum(self.ids, 0)], self.ids).astype(np.int32)
+
+
+# the columns of a tile's partial table (pydem_fill_seam_inventory, SeamFill.inventory), and the key of a double in 'zmin'
+SEAM_TABLE_COLS = ('cells', 'r0', 'r1', 'c0', 'c1', 'zmin', 'bottom', 'pour', 'n_sills', 'open', 'area', 'volume', 'bottom_elev')
 
 
 # ---- depression inventory (no reference method): the host twin of pydem_depressions (csrc/depressions.hip) ----

@@ -526,3 +526,401 @@ int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
     t->depr.swap(rows);
     return 0;
 }
+
+// ---- the inventory ACROSS tiles: the session calls pydem_fill_seam_label / _label_roots / _get_id_lines / _inventory / _labels
+// (include/pydem_hip.h).  The session's W is the tile's window of the whole-mosaic classic fill; the tile labels its own
+// components of W > z with the kernels above, the host joins them across the tiles, and the tile then reduces the cells it OWNS
+// into a partial table whose rows are the mosaic's depressions it can meet.  A cell outside the window comes from the halo ring
+// (2 m + 2 n + 4 cells: the row above over columns -1 .. m, the row below, the column left over rows 0 .. n-1, the column right).
+// Integers only, as above: the host twin (conditioning.SeamFill) gives the same words.
+namespace {
+
+// the partial table: S_COLS columns of n_rows 64-bit words, column-major
+enum { S_CELLS = 0, S_R0, S_R1, S_C0, S_C1, S_ZMIN, S_BOTTOM, S_POUR, S_NSILLS, S_OPEN, S_AREA, S_VOLUME, S_BOTELEV, S_COLS };
+
+// parent (flattened) -> local ids in place, as k_dp_ids; a root stores its cell and its level
+__global__ void __launch_bounds__(256)
+k_ds_ids(int32_t *lab, const int32_t *__restrict__ rank, const double *__restrict__ W, int32_t *__restrict__ roots,
+         double *__restrict__ levels, int64_t K, int64_t NN)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < NN; c += (int64_t)gridDim.x * blockDim.x) {
+        const int p = lab[c];
+        const double w = W[c];
+        int id;
+        if (p >= 0) {
+            id = rank[p] + 1;
+            if (p == (int)c && id <= K) { roots[id - 1] = (int32_t)c; levels[id - 1] = w; }
+        } else
+            id = isnan(w) ? -1 : 0;
+        lab[c] = id;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_ds_gather(const int32_t *__restrict__ src, int64_t pitch, int64_t cnt, int32_t *__restrict__ dst)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i * pitch];
+}
+
+__global__ void __launch_bounds__(256)
+k_ds_table_init(u64 *tab, int64_t T)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * S_COLS) return;
+    const int col = (int)(i / T);
+    const bool is_min = col == S_R0 || col == S_C0 || col == S_ZMIN || col == S_BOTTOM || col == S_POUR;
+    tab[i] = is_min ? ~0ull : 0ull;
+}
+
+// k_dp_stats on the cells the tile owns, with rows through the lookup (several local ids may share a row) and the halo ring
+__global__ void __launch_bounds__(256)
+k_ds_stats(const int32_t *__restrict__ ids, const double *__restrict__ z, const double *__restrict__ W, const uint8_t *__restrict__ outlets,
+           const uint8_t *__restrict__ owner, const int32_t *__restrict__ lut, const int32_t *__restrict__ halo_ids,
+           const double *__restrict__ halo_W, const double *__restrict__ row_area, u64 *tab, int64_t T, int n, int m, int sh_area, int sh_vol)
+{
+    const int64_t NN = (int64_t)n * m;
+    const int lane = (int)(threadIdx.x & 63);
+    for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < NN; c0 += (int64_t)gridDim.x * blockDim.x) {     // (uniform per wavefront)
+        const int64_t c = c0 + threadIdx.x;
+        int l = -1, g = 0, r = 0, q = 0;
+        bool own = false;
+        double zc = 0.0;
+        if (c < NN) {
+            l = ids[c];
+            own = owner[c] != 0;
+            r = (int)(c / m);
+            q = (int)(c - (int64_t)r * m);
+            zc = z[c];
+            if (l > 0) g = lut[l];
+        }
+        const bool up = own && g > 0;
+        u64 zk = ~0ull, ai = 0, vi = 0;
+        if (up) {
+            const double a0 = row_area[r];
+            zk = dp_key(zc + 0.0);
+            ai = (u64)__double2ll_rn(ldexp(a0, sh_area));
+            vi = (u64)__double2ll_rn(ldexp((W[c] - zc) * a0, sh_vol));
+        }
+        u64 todo = __ballot(up);
+        while (todo) {                                          // (todo is the same in every lane)
+            const int leader = __ffsll((long long)todo) - 1;
+            const int lid = __shfl(g, leader);
+            const bool mine = up && g == lid;
+            const u64 mask = __ballot(mine);
+            todo &= ~mask;
+            int rmin = r, rmax = r, qmin = q, qmax = q;
+            u64 cnt = 1, k = zk, a = ai, v = vi;
+            if (mask != (1ull << leader)) {                     // more than one lane: reduce first (uniform branch)
+                rmin = dp_wave_min(mine ? r : 0x7fffffff);
+                rmax = dp_wave_max(mine ? r : -1);
+                qmin = dp_wave_min(mine ? q : 0x7fffffff);
+                qmax = dp_wave_max(mine ? q : -1);
+                k = dp_wave_min(mine ? zk : ~0ull);
+                a = dp_wave_add(mine ? ai : 0ull);
+                v = dp_wave_add(mine ? vi : 0ull);
+                cnt = (u64)__popcll(mask);
+            }
+            if (lane == leader) {
+                u64 *row = tab + (lid - 1);
+                atomicAdd(row + (int64_t)S_CELLS * T, cnt);
+                atomicMin(row + (int64_t)S_R0 * T, (u64)rmin);
+                atomicMax(row + (int64_t)S_R1 * T, (u64)rmax);
+                atomicMin(row + (int64_t)S_C0 * T, (u64)qmin);
+                atomicMax(row + (int64_t)S_C1 * T, (u64)qmax);
+                atomicMin(row + (int64_t)S_ZMIN * T, k);
+                atomicAdd(row + (int64_t)S_AREA * T, a);
+                atomicAdd(row + (int64_t)S_VOLUME * T, v);
+            }
+        }
+        // sills: an owned finite cell that is not raised, beside a depression whose level is this cell's elevation; its whole 3 x 3
+        // is known here, so it is open exactly when a neighbour is no data or uncovered (-1), or when it is an outlet
+        if (c < NN && own && l == 0) {
+            int gs[8];
+            bool open = false;
+            int found = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int dr = j < 3 ? -1 : (j < 5 ? 0 : 1);
+                const int dq = j < 3 ? j - 1 : (j == 3 ? -1 : (j == 4 ? 1 : j - 6));
+                const int rr = r + dr, qq = q + dq;
+                gs[j] = 0;
+                int gv;
+                double wv = 0.0;
+                if (rr >= 0 && rr < n && qq >= 0 && qq < m) {
+                    const int64_t v = (int64_t)rr * m + qq;
+                    const int lv = ids[v];
+                    gv = lv < 0 ? -1 : (lv > 0 ? lut[lv] : 0);
+                    if (gv > 0) wv = W[v];
+                } else {
+                    int h;
+                    if (rr < 0) h = qq + 1;
+                    else if (rr >= n) h = (m + 2) + qq + 1;
+                    else if (qq < 0) h = 2 * (m + 2) + rr;
+                    else h = 2 * (m + 2) + n + rr;
+                    gv = halo_ids[h];
+                    wv = halo_W[h];
+                }
+                if (gv < 0) open = true;
+                else if (gv > 0 && wv == zc) { gs[j] = gv; found = 1; }
+            }
+            if (found) {
+                if (outlets && outlets[c] != 0) open = true;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    bool fresh = gs[j] > 0;
+#pragma unroll
+                    for (int i = 0; i < j; i++) fresh = fresh && gs[i] != gs[j];
+                    if (fresh) {
+                        u64 *row = tab + (gs[j] - 1);
+                        atomicAdd(row + (int64_t)S_NSILLS * T, 1ull);
+                        atomicMin(row + (int64_t)S_POUR * T, (u64)c);
+                        if (open) atomicMax(row + (int64_t)S_OPEN * T, 1ull);
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_ds_bottom(const int32_t *__restrict__ ids, const double *__restrict__ z, const uint8_t *__restrict__ owner, const int32_t *__restrict__ lut,
+            u64 *tab, int64_t T, int64_t NN)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < NN; c += (int64_t)gridDim.x * blockDim.x) {
+        const int l = ids[c];
+        if (l <= 0 || owner[c] == 0) continue;
+        const int g = lut[l];
+        if (g <= 0) continue;
+        if (z[c] == dp_unkey(tab[(int64_t)S_ZMIN * T + g - 1])) atomicMin(tab + (int64_t)S_BOTTOM * T + g - 1, (u64)c);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_ds_botelev(const double *__restrict__ z, u64 *tab, int64_t T, int64_t NN)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= T) return;
+    const u64 b = tab[(int64_t)S_BOTTOM * T + k];
+    if (b < (u64)NN) tab[(int64_t)S_BOTELEV * T + k] = (u64)__double_as_longlong(z[b]);
+}
+
+__global__ void __launch_bounds__(256)
+k_ds_write(const int32_t *__restrict__ ids, const int32_t *__restrict__ lut, int32_t *__restrict__ out, int64_t NN)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < NN; c += (int64_t)gridDim.x * blockDim.x) {
+        const int l = ids[c];
+        out[c] = l > 0 ? lut[l] : l;
+    }
+}
+
+int seam_elapsed(pydem_tile *t, double *ms)
+{
+    HIP_TRY(hipEventRecord(t->ev[7], t->stream));
+    HIP_TRY(hipEventSynchronize(t->ev[7]));
+    float el = 0.f;
+    HIP_TRY(hipEventElapsedTime(&el, t->ev[6], t->ev[7]));
+    if (ms) *ms = (double)el;
+    return 0;
+}
+
+}  // namespace
+
+int stage_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, double *ms)
+{
+    const char *who = "pydem_fill_seam_label";
+    if (!t->fs_open) { pydem_set_error("%s: no session is open on this tile (pydem_fill_seam_begin first)", who); return -2; }
+    if (t->NN >= (int64_t)INT32_MAX) { pydem_set_error("%s: %lld cells do not fit the int32 id plane", who, (long long)t->NN); return -2; }
+    const char *e = getenv("PYDEM_DEPR_LOCAL");                 // read per call: the tests switch it
+    const bool local = !(e && *e && atoi(e) == 0);
+    const int n = (int)t->n, m = (int)t->m;
+    const int64_t NN = t->NN;
+    if (!t->fs_ids) PYDEM_TRY(tile_hold(t, (void **)&t->fs_ids, (size_t)NN * 4, true));
+    t->fs_K = -1;
+    t->fs_roots.clear();
+    t->fs_levels.clear();
+
+    ArenaLease lease;
+    PYDEM_TRY(arena_acquire(t->device, &lease));
+    int32_t *parent = t->fs_ids;
+    int32_t *rank = (int32_t *)arena_take(&lease, (size_t)NN * 4);
+    u64 *ctr = (u64 *)arena_take(&lease, DPC_WORDS * 8);
+    size_t scan_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)NN, t->stream));
+    void *scan_tmp = arena_take(&lease, scan_bytes);
+    if (!rank || !ctr || !scan_tmp) return -1;
+    const double *W = t->fs_W;
+    const double *z = t->elev;
+    const int gcells = (int)(cdiv(NN, 256) < 8192 ? cdiv(NN, 256) : 8192);
+    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
+    HIP_TRY(hipEventRecord(t->ev[6], t->stream));
+    HIP_TRY(hipMemsetAsync(ctr, 0, DPC_WORDS * 8, t->stream));
+    hipLaunchKernelGGL(k_dp_init, dim3(gcells), dim3(256), 0, t->stream, z, W, parent, NN, ctr);
+    if (local) hipLaunchKernelGGL(k_dp_local, dim3((unsigned)cdiv(m, DP_B), (unsigned)cdiv(n, DP_B)), dim3(DP_T), 0, t->stream, parent, n, m);
+    hipLaunchKernelGGL(k_dp_merge, dim3(gfull), dim3(256), 0, t->stream, parent, n, m, local ? 0 : 1);
+    hipLaunchKernelGGL(k_dp_flatten, dim3(gfull), dim3(256), 0, t->stream, parent, rank, NN);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, rank, rank, (int)NN, t->stream));
+    // K and the largest depth.  A seam cell may be raised, the tile's last cell included: it counts when it is its own root
+    volatile u64 *h = (volatile u64 *)t->h_counters;
+    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, 8, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_counters + 2, rank + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_counters + 3, parent + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    const double depth_max = as_double(h[DPC_DEPTH]);
+    const int64_t K = (int64_t)t->h_counters[2] + ((int64_t)t->h_counters[3] == NN - 1 ? 1 : 0);
+    if (K < 0 || K > NN) { pydem_set_error("%s: inconsistent count of depressions (%lld)", who, (long long)K); return -5; }
+    if (!std::isfinite(depth_max)) {
+        pydem_set_error("%s: cells of W are still +inf (no relaxation has reached them); nothing was labelled", who);
+        return -5;
+    }
+    int32_t *roots = nullptr;
+    double *levels = nullptr;
+    if (K > 0) {
+        roots = (int32_t *)arena_take(&lease, (size_t)K * 4);
+        levels = (double *)arena_take(&lease, (size_t)K * 8);
+        if (!roots || !levels) return -1;
+    }
+    hipLaunchKernelGGL(k_ds_ids, dim3(gfull), dim3(256), 0, t->stream, parent, (const int32_t *)rank, W, roots, levels, K, NN);
+    HIP_TRY(hipGetLastError());
+    PYDEM_TRY(seam_elapsed(t, ms));
+    if (K > 0) {
+        t->fs_roots.resize((size_t)K);
+        t->fs_levels.resize((size_t)K);
+        PYDEM_TRY(tile_plane_copy(t, roots, t->fs_roots.data(), (size_t)K * 4, true));
+        PYDEM_TRY(tile_plane_copy(t, levels, t->fs_levels.data(), (size_t)K * 8, true));
+    }
+    t->fs_K = K;
+    if (n_local) *n_local = K;
+    if (max_depth) *max_depth = depth_max;
+    return 0;
+}
+
+int stage_fill_seam_label_roots(pydem_tile *t, int64_t count, int32_t *roots, double *levels)
+{
+    const char *who = "pydem_fill_seam_label_roots";
+    if (!t->fs_open || t->fs_K < 0) { pydem_set_error("%s: the open session has no labels (pydem_fill_seam_label first)", who); return -2; }
+    if (count != t->fs_K || (count > 0 && (!roots || !levels))) {
+        pydem_set_error("%s: %lld entries asked, pydem_fill_seam_label found %lld", who, (long long)count, (long long)t->fs_K);
+        return -2;
+    }
+    if (count > 0) {
+        memcpy(roots, t->fs_roots.data(), (size_t)count * 4);
+        memcpy(levels, t->fs_levels.data(), (size_t)count * 8);
+    }
+    return 0;
+}
+
+int stage_fill_seam_get_id_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts)
+{
+    const char *who = "pydem_fill_seam_get_id_lines";
+    if (!t->fs_open || t->fs_K < 0) { pydem_set_error("%s: the open session has no labels (pydem_fill_seam_label first)", who); return -2; }
+    if (count <= 0) return 0;
+    const size_t Lmax = (size_t)(t->n > t->m ? t->n : t->m);
+    int ncols = 0;
+    for (int k = 0; k < count; k++) {
+        const int64_t lim = axes[k] == 0 ? t->n : t->m;
+        if ((axes[k] != 0 && axes[k] != 1) || indices[k] < -lim || indices[k] >= lim) { pydem_set_error("%s: line index out of range", who); return -2; }
+        if (axes[k] == 1) ncols++;
+    }
+    ArenaLease lease;
+    int32_t *stage = nullptr;
+    if (ncols) {
+        PYDEM_TRY(arena_acquire(t->device, &lease));
+        stage = (int32_t *)arena_take(&lease, (size_t)ncols * (size_t)t->n * 4);
+        if (!stage) return -1;
+    }
+    void *pin_v = nullptr;
+    PYDEM_TRY(tile_pinned(t, (size_t)count * Lmax * 4, &pin_v));
+    char *pin = (char *)pin_v;
+    int col = 0;
+    for (int k = 0; k < count; k++) {
+        const int64_t lim = axes[k] == 0 ? t->n : t->m;
+        const int64_t index = indices[k] < 0 ? indices[k] + lim : indices[k];
+        if (axes[k] == 0) {
+            HIP_TRY(hipMemcpyAsync(pin + (size_t)k * Lmax * 4, t->fs_ids + (size_t)index * t->m, (size_t)t->m * 4, hipMemcpyDeviceToHost, t->stream));
+        } else {
+            int32_t *dst = stage + (size_t)col++ * (size_t)t->n;
+            const int g = (int)(cdiv(t->n, 256) < 64 ? cdiv(t->n, 256) : 64);
+            hipLaunchKernelGGL(k_ds_gather, dim3(g), dim3(256), 0, t->stream, (const int32_t *)(t->fs_ids + index), t->m, t->n, dst);
+            HIP_TRY(hipMemcpyAsync(pin + (size_t)k * Lmax * 4, dst, (size_t)t->n * 4, hipMemcpyDeviceToHost, t->stream));
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    for (int k = 0; k < count; k++) memcpy(dsts[k], pin + (size_t)k * Lmax * 4, (size_t)(axes[k] == 0 ? t->m : t->n) * 4);
+    return 0;
+}
+
+int stage_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t T, const uint8_t *owner, const uint8_t *outlets,
+                              const int32_t *halo_ids, const double *halo_W, const double *row_area, int sh_area, int sh_vol,
+                              uint64_t *table, double *ms)
+{
+    const char *who = "pydem_fill_seam_inventory";
+    if (!t->fs_open || t->fs_K < 0) { pydem_set_error("%s: the open session has no labels (pydem_fill_seam_label first)", who); return -2; }
+    const int n = (int)t->n, m = (int)t->m;
+    const int64_t NN = t->NN, K = t->fs_K;
+    const size_t R = 2 * (size_t)m + 2 * (size_t)n + 4;
+    if (!lut || !owner || !halo_ids || !halo_W || !row_area || (T > 0 && !table)) { pydem_set_error("%s: a NULL argument", who); return -2; }
+    if (T < 0 || T >= (int64_t)INT32_MAX) { pydem_set_error("%s: %lld rows do not fit int32 ids", who, (long long)T); return -2; }
+    // every index the kernels form from these is checked here: a row is 1 .. T
+    for (int64_t k = 0; k <= K; k++)
+        if (lut[k] < 0 || lut[k] > T) { pydem_set_error("%s: lookup entry %lld is %d, outside 0 .. %lld", who, (long long)k, lut[k], (long long)T); return -2; }
+    for (size_t e = 0; e < R; e++)
+        if (halo_ids[e] < -1 || halo_ids[e] > T) { pydem_set_error("%s: halo entry %zu is %d, outside -1 .. %lld", who, e, halo_ids[e], (long long)T); return -2; }
+    if (ms) *ms = 0.0;
+    if (T == 0) return 0;
+
+    ArenaLease lease;
+    PYDEM_TRY(arena_acquire(t->device, &lease));
+    int32_t *d_lut = (int32_t *)arena_take(&lease, (size_t)(K + 1) * 4);
+    uint8_t *d_owner = (uint8_t *)arena_take(&lease, (size_t)NN);
+    uint8_t *d_out = outlets ? (uint8_t *)arena_take(&lease, (size_t)NN) : nullptr;
+    int32_t *d_hid = (int32_t *)arena_take(&lease, R * 4);
+    double *d_hW = (double *)arena_take(&lease, R * 8);
+    double *d_ra = (double *)arena_take(&lease, (size_t)n * 8);
+    u64 *tab = (u64 *)arena_take(&lease, (size_t)T * S_COLS * 8);
+    if (!d_lut || !d_owner || (outlets && !d_out) || !d_hid || !d_hW || !d_ra || !tab) return -1;
+    PYDEM_TRY(tile_plane_copy(t, d_lut, const_cast<int32_t *>(lut), (size_t)(K + 1) * 4, false));
+    PYDEM_TRY(tile_plane_copy(t, d_owner, const_cast<uint8_t *>(owner), (size_t)NN, false));
+    if (outlets) PYDEM_TRY(tile_plane_copy(t, d_out, const_cast<uint8_t *>(outlets), (size_t)NN, false));
+    PYDEM_TRY(tile_plane_copy(t, d_hid, const_cast<int32_t *>(halo_ids), R * 4, false));
+    PYDEM_TRY(tile_plane_copy(t, d_hW, const_cast<double *>(halo_W), R * 8, false));
+    PYDEM_TRY(tile_plane_copy(t, d_ra, const_cast<double *>(row_area), (size_t)n * 8, false));
+
+    const int gcells = (int)(cdiv(NN, 256) < 8192 ? cdiv(NN, 256) : 8192);
+    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
+    const double *z = t->elev;
+    HIP_TRY(hipEventRecord(t->ev[6], t->stream));
+    hipLaunchKernelGGL(k_ds_table_init, dim3((unsigned)cdiv(T * S_COLS, 256)), dim3(256), 0, t->stream, tab, T);
+    hipLaunchKernelGGL(k_ds_stats, dim3(gcells), dim3(256), 0, t->stream, (const int32_t *)t->fs_ids, z, (const double *)t->fs_W,
+                       (const uint8_t *)d_out, (const uint8_t *)d_owner, (const int32_t *)d_lut, (const int32_t *)d_hid, (const double *)d_hW,
+                       (const double *)d_ra, tab, T, n, m, sh_area, sh_vol);
+    hipLaunchKernelGGL(k_ds_bottom, dim3(gfull), dim3(256), 0, t->stream, (const int32_t *)t->fs_ids, z, (const uint8_t *)d_owner,
+                       (const int32_t *)d_lut, tab, T, NN);
+    hipLaunchKernelGGL(k_ds_botelev, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, t->stream, z, tab, T, NN);
+    HIP_TRY(hipGetLastError());
+    PYDEM_TRY(seam_elapsed(t, ms));
+    PYDEM_TRY(tile_plane_copy(t, tab, table, (size_t)T * S_COLS * 8, true));
+    return 0;
+}
+
+int stage_fill_seam_labels(pydem_tile *t, const int32_t *lut, int32_t *label, double *ms)
+{
+    const char *who = "pydem_fill_seam_labels";
+    if (!t->fs_open || t->fs_K < 0) { pydem_set_error("%s: the open session has no labels (pydem_fill_seam_label first)", who); return -2; }
+    if (!lut || !label) { pydem_set_error("%s: a NULL argument", who); return -2; }
+    const int64_t NN = t->NN, K = t->fs_K;
+    ArenaLease lease;
+    PYDEM_TRY(arena_acquire(t->device, &lease));
+    int32_t *d_lut = (int32_t *)arena_take(&lease, (size_t)(K + 1) * 4);
+    int32_t *out = (int32_t *)arena_take(&lease, (size_t)NN * 4);
+    if (!d_lut || !out) return -1;
+    PYDEM_TRY(tile_plane_copy(t, d_lut, const_cast<int32_t *>(lut), (size_t)(K + 1) * 4, false));
+    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
+    HIP_TRY(hipEventRecord(t->ev[6], t->stream));
+    hipLaunchKernelGGL(k_ds_write, dim3(gfull), dim3(256), 0, t->stream, (const int32_t *)t->fs_ids, (const int32_t *)d_lut, out, NN);
+    HIP_TRY(hipGetLastError());
+    PYDEM_TRY(seam_elapsed(t, ms));
+    PYDEM_TRY(tile_plane_copy(t, out, label, (size_t)NN * 4, true));
+    return 0;
+}

@@ -465,6 +465,10 @@ static void fill_seam_drop(pydem_tile *t)
     tile_drop(t, (void **)&t->fs_W);
     tile_drop(t, (void **)&t->fs_flags);
     tile_drop(t, (void **)&t->fs_caps);
+    tile_drop(t, (void **)&t->fs_ids);          // (the id plane of pydem_fill_seam_label, where one is held)
+    t->fs_K = -1;
+    t->fs_roots.clear();
+    t->fs_levels.clear();
     t->fs_caps_h.clear();
     t->fs_open = false;
 }

@@ -147,6 +147,12 @@ struct pydem_tile {
     std::vector<double> fs_caps_h;
     bool fs_open = false;
     double fs_amax = 0.0, fs_eps = -1.0;
+    // the session's inventory part (depressions.hip: pydem_fill_seam_label ...): the plane of local ids 1..fs_K (0 not raised, -1 no
+    // data), held from the label call to the end of the session; each local depression's first cell and level (host memory)
+    int32_t *fs_ids = nullptr;
+    int64_t fs_K = -1;                      // -1: not labelled yet
+    std::vector<int32_t> fs_roots;
+    std::vector<double> fs_levels;
     std::vector<pydem_depression> depr;     // the table of the last pydem_depressions (host memory; pydem_depressions_table copies it out)
     std::vector<TileBlock> blocks;  // every device block the members above point to; device_bytes is their sum (both written by tile_mem.h only)
     int64_t device_bytes = 0;
@@ -229,6 +235,15 @@ int stage_fill_seam_begin(pydem_tile *t, const uint8_t *outlets, const uint8_t *
 int stage_fill_seam_relax(pydem_tile *t, double eps, const double *const caps[4], int64_t *n_lowered, int64_t *passes, double *ms);
 int stage_fill_seam_get_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts);
 int stage_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_raised, double *max_depth);
+// the inventory part of the seam session (depressions.hip): local components of the session's W, lines of their id plane, the
+// tile's partial table over the cells it owns, the label plane through a lookup
+int stage_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, double *ms);
+int stage_fill_seam_label_roots(pydem_tile *t, int64_t count, int32_t *roots, double *levels);
+int stage_fill_seam_get_id_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts);
+int stage_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t n_rows, const uint8_t *owner, const uint8_t *outlets,
+                              const int32_t *halo_ids, const double *halo_W, const double *row_area, int shift_area, int shift_volume,
+                              uint64_t *table, double *ms);
+int stage_fill_seam_labels(pydem_tile *t, const int32_t *lut, int32_t *label, double *ms);
 int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
                       int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms);
 int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);

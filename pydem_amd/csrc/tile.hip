@@ -544,6 +544,38 @@ int pydem_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_rai
     return rc;
 }
 
+// the session's inventory part (depressions.hip): these read the elevation and the session's W and change nothing else of the tile
+int pydem_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, double *ms)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    return stage_fill_seam_label(t, n_local, max_depth, ms);
+}
+
+int pydem_fill_seam_label_roots(pydem_tile *t, int64_t count, int32_t *roots, double *levels)
+{
+    return stage_fill_seam_label_roots(t, count, roots, levels);
+}
+
+int pydem_fill_seam_get_id_lines(pydem_tile *t, int count, const int *axes, const int64_t *indices, void *const *dsts)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    return stage_fill_seam_get_id_lines(t, count, axes, indices, dsts);
+}
+
+int pydem_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t n_rows, const uint8_t *owner, const uint8_t *outlets,
+                              const int32_t *halo_ids, const double *halo_W, const double *row_area, int shift_area, int shift_volume,
+                              uint64_t *table, double *ms)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    return stage_fill_seam_inventory(t, lut, n_rows, owner, outlets, halo_ids, halo_W, row_area, shift_area, shift_volume, table, ms);
+}
+
+int pydem_fill_seam_labels(pydem_tile *t, const int32_t *lut, int32_t *label, double *ms)
+{
+    HIP_TRY(hipSetDevice(t->device));
+    return stage_fill_seam_labels(t, lut, label, ms);
+}
+
 int pydem_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
                       int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms)
 {

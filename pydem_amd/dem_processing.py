@@ -475,6 +475,7 @@ class DEMProcessor(FlowAnalyses):
     # ---- the fill across tiles: this tile's session (include/pydem_hip.h: pydem_fill_seam_*; no counterpart in the reference).
     # ProcessManager.process_fill_depressions drives it: begin on every tile, rounds of line exchange and relax, end.
     _seam_host = None             # the host twin serving the open session (conditioning.SeamFill), where the device does not take the tile
+    _seam_outlets = None          # the outlets mask of the open session
     _seam_open = False
 
     def fill_seam_begin(self, seam, outlets=None):
@@ -501,6 +502,7 @@ class DEMProcessor(FlowAnalyses):
             self._ensure_tile()
             self._push('elev')
             amax = self._tile.fill_seam_begin(seam, mask)
+        self._seam_outlets = mask           # (fill_seam_inventory gives them to the library again)
         self._seam_open = True
         self._seam_stats = dict(epsilon=None, passes=0, ms=0.0)
         return amax
@@ -530,6 +532,43 @@ class DEMProcessor(FlowAnalyses):
         if self._seam_host is not None:
             return self._seam_host.lines(requests)
         return self._tile.fill_seam_lines(requests)
+
+    # the session's inventory part (ProcessManager.process_depressions drives it once no cap falls at epsilon 0); 'ms' is 0 where
+    # the host twin serves the session
+    def fill_seam_label(self):
+        """Label the components of W > z inside the tile: {'roots', 'levels', 'max_depth', 'ms'} -- the first cell (linear index) and
+        the level of each local component, in the order of their local ids 1 .. len(roots), and the tile's largest depth."""
+        self._seam_check('fill_seam_label')
+        if self._seam_host is not None:
+            roots, levels, dmax = self._seam_host.label()
+            return dict(roots=roots, levels=levels, max_depth=dmax, ms=0.0)
+        roots, levels, dmax, ms = self._tile.fill_seam_label()
+        return dict(roots=roots, levels=levels, max_depth=dmax, ms=ms)
+
+    def fill_seam_id_lines(self, requests):
+        """[(axis, index)] -> rows and columns of the plane of local ids (int32: 0 not raised, -1 no data)"""
+        self._seam_check('fill_seam_id_lines')
+        if self._seam_host is not None:
+            return self._seam_host.id_lines(requests)
+        return self._tile.fill_seam_id_lines(requests)
+
+    def fill_seam_inventory(self, lut, n_rows, owner, halo_ids, halo_W, row_area, shift_area, shift_volume):
+        """The tile's partial table of the mosaic's depressions over the cells `owner` marks (include/pydem_hip.h:
+        pydem_fill_seam_inventory; columns: conditioning.SEAM_TABLE_COLS): {'table': uint64 [13, n_rows], 'ms'}.  The outlets are
+        those of fill_seam_begin."""
+        self._seam_check('fill_seam_inventory')
+        if self._seam_host is not None:
+            return dict(table=self._seam_host.inventory(lut, n_rows, owner, halo_ids, halo_W, row_area, shift_area, shift_volume), ms=0.0)
+        table, ms = self._tile.fill_seam_inventory(lut, n_rows, owner, halo_ids, halo_W, row_area, shift_area, shift_volume, self._seam_outlets)
+        return dict(table=table, ms=ms)
+
+    def fill_seam_labels(self, lut):
+        """The label plane through a lookup from local ids: {'label': int32 [n, m], 'ms'}"""
+        self._seam_check('fill_seam_labels')
+        if self._seam_host is not None:
+            return dict(label=self._seam_host.labels(lut), ms=0.0)
+        label, ms = self._tile.fill_seam_labels(lut)
+        return dict(label=label, ms=ms)
 
     def fill_seam_end(self, commit=True, return_depth=False):
         """Close the session.  commit: the elevation becomes W, with the dtype rule, the stale fields and `fill_depressions_stats`
@@ -589,7 +628,8 @@ class DEMProcessor(FlowAnalyses):
         be cut by the tile), area and volume (fixed-point sums with one result, in the units of dX * dY and z * dX * dY; their
         quanta are in `depressions_stats`) and mean_depth = volume / area.  Depressions below min_depth, min_cells or min_volume
         are dropped and the rest renumbered in the same order.  The elevation, its dtype and everything computed from it stay
-        as they are.  Per tile: a depression cut by the tile's border is open there; the nested hierarchy is not computed."""
+        as they are.  Per tile: a depression cut by the tile's border is open there (ProcessManager.process_depressions takes the
+        mosaic); the nested hierarchy is not computed."""
         from . import conditioning
         lim = conditioning.depression_limits("calc_depressions", min_depth=min_depth, min_cells=min_cells, min_volume=min_volume)
         if any(v is None for v in lim.values()):

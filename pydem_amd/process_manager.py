@@ -587,13 +587,32 @@ class ProcessManager(object):
         aborted and the error raised: no elevation has changed.  Needs one pixel size, overlap >= 1 and all tiles in this
         process (NotImplementedError before any tile is touched)."""
         from . import conditioning
+        lat, seams, links, owned, per_tile_outlets = self._fill_plan("process_fill_depressions", outlets)
+        if epsilon is not None:
+            epsilon = conditioning.fill_depressions_epsilon(np.zeros(1), epsilon)       # (type and range; the magnitude below)
+        begun = []
+        try:
+            eps, rounds = self._fill_sessions("process_fill_depressions", owned, seams, links, per_tile_outlets, epsilon, max_rounds, begun)
+            for i in owned:
+                self.tiles[i].fill_seam_end(True)
+                begun.remove(i)
+                if self.checkpoint:
+                    self._store(i, 'elev', {'elev': np.asarray(self.tiles[i].elev, float)})
+        except BaseException:
+            self._fill_abort("process_fill_depressions", begun)
+            raise
+        self.fill_rounds = rounds
+        self.fill_depressions_epsilon_used = eps
+        return [1] * self.n_inputs
+
+    def _fill_plan(self, who, outlets):
+        """What a run of the seam sessions needs, with its refusals (before any tile is touched): the lattice, the seam lines and
+        links, the tiles, and the outlets (lattice (row, col) pairs) as local pairs per tile."""
         lat = self.fill_lattice()
         seams, links = self._fill_seams(lat)
         owned = list(self._owned())
         if len(owned) != self.n_inputs:
-            raise NotImplementedError("process_fill_depressions: every tile must belong to this process (multi-rank runs are not supported)")
-        if epsilon is not None:
-            epsilon = conditioning.fill_depressions_epsilon(np.zeros(1), epsilon)       # (type and range; the magnitude below)
+            raise NotImplementedError("%s: every tile must belong to this process (multi-rank runs are not supported)" % who)
         per_tile_outlets = [None] * self.n_inputs
         if outlets is not None:
             cells = np.asarray(outlets, np.int64).reshape(-1, 2)
@@ -602,63 +621,276 @@ class ProcessManager(object):
                 ok = (rr >= 0) & (rr < lat[i, 2]) & (cc >= 0) & (cc < lat[i, 3])
                 if ok.any():
                     per_tile_outlets[i] = np.stack([rr[ok], cc[ok]], axis=1)
+        return lat, seams, links, owned, per_tile_outlets
+
+    def _fill_sessions(self, who, owned, seams, links, per_tile_outlets, epsilon, max_rounds, begun):
+        """Open a seam session on every tile (each joins `begun` as it opens) and run the Jacobi rounds to the point where no cap
+        falls: every session then holds its window of the whole-mosaic fill.  Returns (epsilon used, rounds); the sessions stay
+        open, for the caller to commit or abort."""
+        from . import conditioning
         if all(self.tiles[i] is None for i in owned):
             self.process_elevation()
+        amax = 0.0
+        for i in owned:
+            amax = max(amax, float(self.tiles[i].fill_seam_begin(seams[i], per_tile_outlets[i])))
+            begun.append(i)
+        eps = conditioning.fill_depressions_epsilon(np.array([amax]), epsilon)
+        # the lines of W that other tiles read, per tile
+        wanted = {j: sorted(set((lk[3], lk[4]) for i in owned for lk in links[i] if lk[2] == j)) for j in owned}
+        caps = {i: {side: np.full(seams[i][side].shape, np.inf) for side in SIDES} for i in owned}
+        rounds = 0
+        log = self.fill_round_log = []          # per round: tiles relaxed, cells that fell, passes, device ms (summed over the tiles), wall ms
+        while True:
+            snap = {}
+            for j in owned:
+                if wanted[j]:
+                    snap.update({(j,) + key: line for key, line in zip(wanted[j], self.tiles[j].fill_seam_lines(wanted[j]))})
+            todo = {}
+            for i in owned:
+                new = {side: np.full(seams[i][side].shape, np.inf) for side in SIDES}
+                for side, mine, j, axis, index, theirs in links[i]:
+                    seg = snap[(j, axis, index)][theirs]
+                    new[side][mine] = np.fmin(new[side][mine], np.where(np.isnan(seg), np.inf, seg))
+                fell = False
+                for side in SIDES:
+                    new[side][~seams[i][side]] = np.inf             # (only a seam cell is capped)
+                    fell = fell or bool((new[side] < caps[i][side]).any())
+                if fell or rounds == 0:
+                    todo[i] = new
+            if not todo:
+                break
+            if rounds >= max_rounds:
+                raise RuntimeError("%s: caps still fall after %d rounds (max_rounds)" % (who, rounds))
+            caps.update(todo)
+            got = {}
+            t0 = time.perf_counter()
+            self._per_tile(lambda i: got.__setitem__(i, self.tiles[i].fill_seam_relax(eps, todo[i])) if i in todo else None)
+            log.append(dict(tiles=len(todo), n_lowered=sum(g['n_lowered'] for g in got.values()), passes=sum(g['passes'] for g in got.values()),
+                            device_ms=sum(g['ms'] for g in got.values()), wall_ms=(time.perf_counter() - t0) * 1e3))
+            rounds += 1
+        return eps, rounds
+
+    def _fill_abort(self, who, begun):
+        for i in list(begun):
+            try:
+                self.tiles[i].fill_seam_end(False)
+                begun.remove(i)
+            except Exception:
+                logger.exception("%s: could not abort the session of tile %d", who, i)
+
+    # ------------------------------------------------------------------ depression inventory across tiles
+    # With epsilon 0 and no cap falling, every session holds its window of the classic fill W of the mosaic.  Each tile labels its
+    # own components of W > z; a component that leaves a tile's window leaves it through a raised cell of a border line that
+    # another tile holds too (a raised cell is never open, so its 3 x 3 is covered, and `_fill_seams` has made sure that two such
+    # neighbours share a tile), so joining the local ids along the links of `_fill_seams` gives the mosaic's components.  A
+    # depression that lies wholly inside a wide overlap is labelled in both tiles and no link joins the copies: components are
+    # therefore identified by their smallest lattice index, and statistics count a lattice cell once, in the lowest-index tile
+    # that holds it (its owner), with the cells just outside the window from the tiles that hold them.
+    depressions = None                   # {'table', 'labels'} of the last process_depressions
+    depressions_stats = None             # its {'n_found', 'quanta', 'fill_rounds', 'ms': {'fill', 'label', 'inventory', 'labels'}}
+
+    def process_depressions(self, outlets=None, min_depth=0.0, min_cells=1, min_volume=0.0, return_labels=True, max_rounds=10000):
+        """The depression inventory of the MOSAIC (calc_depressions takes a tile alone and cuts every lake at the tile's border):
+        {'table', 'labels'}, kept as `depressions`, equal to conditioning.label_depressions of the stitched raster on the lattice
+        of `fill_lattice` (NaN where no tile holds a cell), with one cell area per lattice row: dX2 * dY2 of the lowest-index tile
+        that holds the row.  `table` (conditioning.DEPRESSION_DTYPE) has every row and column in lattice coordinates, numbered by
+        the smallest lattice linear index; `open_sill` says that a lake spills off the mosaic, into no data or into an outlet;
+        area and volume are fixed-point sums whose quanta (in `depressions_stats`) come from the lattice's cell count, the largest
+        row area and the largest depth of the mosaic.  `labels[i]` is tile i's window of the label raster (int32, 0: no kept
+        depression, -1: no data; None without return_labels).  outlets: lattice (row, col) pairs; min_depth, min_cells, min_volume
+        as in calc_depressions.  The seam sessions of process_fill_depressions run at epsilon 0 and are aborted at the end, on
+        success as on any error (RuntimeError after `max_rounds` rounds): no elevation, dtype or field of a tile changes.  The
+        same limits (NotImplementedError before any tile is touched)."""
+        from . import conditioning
+        who = "process_depressions"
+        lim = conditioning.depression_limits(who, min_depth=min_depth, min_cells=min_cells, min_volume=min_volume)
+        if any(v is None for v in lim.values()):
+            raise ValueError("%s: min_depth, min_cells and min_volume must be numbers >= 0" % who)
+        lat, seams, links, owned, per_tile_outlets = self._fill_plan(who, outlets)
         begun = []
         try:
-            amax = 0.0
-            for i in owned:
-                amax = max(amax, float(self.tiles[i].fill_seam_begin(seams[i], per_tile_outlets[i])))
-                begun.append(i)
-            eps = conditioning.fill_depressions_epsilon(np.array([amax]), epsilon)
-            # the lines of W that other tiles read, per tile
-            wanted = {j: sorted(set((lk[3], lk[4]) for i in owned for lk in links[i] if lk[2] == j)) for j in owned}
-            caps = {i: {side: np.full(seams[i][side].shape, np.inf) for side in SIDES} for i in owned}
-            rounds = 0
-            log = self.fill_round_log = []          # per round: tiles relaxed, cells that fell, passes, device ms (summed over the tiles), wall ms
-            while True:
-                snap = {}
-                for j in owned:
-                    if wanted[j]:
-                        snap.update({(j,) + key: line for key, line in zip(wanted[j], self.tiles[j].fill_seam_lines(wanted[j]))})
-                todo = {}
-                for i in owned:
-                    new = {side: np.full(seams[i][side].shape, np.inf) for side in SIDES}
-                    for side, mine, j, axis, index, theirs in links[i]:
-                        seg = snap[(j, axis, index)][theirs]
-                        new[side][mine] = np.fmin(new[side][mine], np.where(np.isnan(seg), np.inf, seg))
-                    fell = False
-                    for side in SIDES:
-                        new[side][~seams[i][side]] = np.inf             # (only a seam cell is capped)
-                        fell = fell or bool((new[side] < caps[i][side]).any())
-                    if fell or rounds == 0:
-                        todo[i] = new
-                if not todo:
-                    break
-                if rounds >= max_rounds:
-                    raise RuntimeError("process_fill_depressions: caps still fall after %d rounds (max_rounds)" % rounds)
-                caps.update(todo)
-                got = {}
-                t0 = time.perf_counter()
-                self._per_tile(lambda i: got.__setitem__(i, self.tiles[i].fill_seam_relax(eps, todo[i])) if i in todo else None)
-                log.append(dict(tiles=len(todo), n_lowered=sum(g['n_lowered'] for g in got.values()), passes=sum(g['passes'] for g in got.values()),
-                                device_ms=sum(g['ms'] for g in got.values()), wall_ms=(time.perf_counter() - t0) * 1e3))
-                rounds += 1
-            for i in owned:
-                self.tiles[i].fill_seam_end(True)
-                begun.remove(i)
-                if self.checkpoint:
-                    self._store(i, 'elev', {'elev': np.asarray(self.tiles[i].elev, float)})
-        except BaseException:
-            for i in begun:
-                try:
-                    self.tiles[i].fill_seam_end(False)
-                except Exception:
-                    logger.exception("process_fill_depressions: could not abort the session of tile %d", i)
-            raise
-        self.fill_rounds = rounds
-        self.fill_depressions_epsilon_used = eps
-        return [1] * self.n_inputs
+            _, rounds = self._fill_sessions(who, owned, seams, links, per_tile_outlets, 0.0, max_rounds, begun)
+            fill_ms = sum(r['device_ms'] for r in self.fill_round_log)
+            table, labels, stats = self._depressions_of_sessions(lat, links, lim, return_labels)
+        finally:
+            self._fill_abort(who, begun)
+        stats['fill_rounds'] = rounds
+        stats['ms']['fill'] = fill_ms
+        self.depressions = dict(table=table, labels=labels)
+        self.depressions_stats = stats
+        return self.depressions
+
+    @staticmethod
+    def _line_sources(lat, i, axis, x, a0, a1):
+        """The tiles other than i that hold a part of the lattice line `x` (a row for axis 0, a column for axis 1) over a0 .. a1 - 1:
+        [(slice into that stretch, tile, local line index, slice into the tile's line)]"""
+        out = []
+        for j in range(lat.shape[0]):
+            if j == i:
+                continue
+            r0, c0, n, m = [int(v) for v in lat[j]]
+            x0, nx, b0, nb = (r0, n, c0, m) if axis == 0 else (c0, m, r0, n)
+            lo, hi = max(a0, b0), min(a1, b0 + nb)
+            if x0 <= x < x0 + nx and lo < hi:
+                out.append((slice(lo - a0, hi - a0), j, x - x0, slice(lo - b0, hi - b0)))
+        return out
+
+    def _depressions_of_sessions(self, lat, links, lim, return_labels):
+        """The inventory from the open sessions (each at the fixed point of the whole-mosaic classic fill): (table, labels, stats)"""
+        from . import conditioning
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        nt = self.n_inputs
+        N, M = int((lat[:, 0] + lat[:, 2]).max()), int((lat[:, 1] + lat[:, 3]).max())
+        ms = dict(label=0.0, inventory=0.0, labels=0.0)
+        # 1. local components
+        local = [None] * nt
+        self._per_tile(lambda i: local.__setitem__(i, self.tiles[i].fill_seam_label()))
+        ms['label'] = sum(l['ms'] for l in local)
+        off = np.concatenate(([0], np.cumsum([l['roots'].size for l in local]))).astype(np.int64)
+        root_lat = np.concatenate([(lat[i, 0] + l['roots'].astype(np.int64) // lat[i, 3]) * M + lat[i, 1] + l['roots'].astype(np.int64) % lat[i, 3]
+                                   for i, l in enumerate(local)] + [np.zeros(0, np.int64)])
+        level = np.concatenate([l['levels'] for l in local] + [np.zeros(0)])
+        # 2. the lines the merge and the halo rings read: a tile's own border lines, the other tiles' copies of them, and the
+        # lines just outside every window
+        own_line = {'top': (0, 0), 'bottom': (0, -1), 'left': (1, 0), 'right': (1, -1)}
+        rings = []
+        wanted = {j: set() for j in range(nt)}
+        for i in range(nt):
+            r0, c0, n, m = [int(v) for v in lat[i]]
+            wanted[i].update((axis, index % (n if axis == 0 else m)) for axis, index in own_line.values())
+            for lk in links[i]:
+                wanted[lk[2]].add((lk[3], lk[4]))
+            # ring stretches in the order of the halo: above, below (columns c0 - 1 .. c0 + m), left, right (rows r0 .. r0 + n - 1)
+            ring = [(0, 0, r0 - 1, c0 - 1, c0 + m + 1), (m + 2, 0, r0 + n, c0 - 1, c0 + m + 1),
+                    (2 * m + 4, 1, c0 - 1, r0, r0 + n), (2 * m + 4 + n, 1, c0 + m, r0, r0 + n)]
+            rings.append([(start, self._line_sources(lat, i, axis, x, a0, a1)) for start, axis, x, a0, a1 in ring])
+        for i in range(nt):
+            for k, (start, parts) in enumerate(rings[i]):
+                for _, j, index, _ in parts:
+                    wanted[j].add((0 if k < 2 else 1, index))
+        idl, Wl = {}, {}
+        for j in range(nt):
+            req = sorted(wanted[j])
+            idl.update({(j,) + key: line for key, line in zip(req, self.tiles[j].fill_seam_id_lines(req))})
+            ring_req = sorted(set((0 if k < 2 else 1, index) for i in range(nt) for k, (_, parts) in enumerate(rings[i])
+                                  for _, jj, index, _ in parts if jj == j))
+            Wl.update({(j,) + key: line for key, line in zip(ring_req, self.tiles[j].fill_seam_lines(ring_req))})
+        # 3. join the local components along the links; a mosaic component is known by its smallest lattice index
+        ea, eb = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+        for i in range(nt):
+            n, m = int(lat[i, 2]), int(lat[i, 3])
+            for side, mine, j, axis, index, theirs in links[i]:
+                oa, oi = own_line[side]
+                a = idl[(i, oa, oi % (n if oa == 0 else m))][mine].astype(np.int64)
+                b = idl[(j, axis, index)][theirs].astype(np.int64)
+                if ((a > 0) != (b > 0)).any():
+                    raise RuntimeError("process_depressions: tiles %d and %d disagree about the raised cells of a shared line" % (i, j))
+                sel = a > 0
+                ea.append(off[i] + a[sel] - 1)
+                eb.append(off[j] + b[sel] - 1)
+        nn = int(off[-1])
+        ea, eb = np.concatenate(ea), np.concatenate(eb)
+        if nn:
+            ncomp, comp = connected_components(coo_matrix((np.ones(ea.size, np.int8), (ea, eb)), shape=(nn, nn)), directed=False)
+            first = np.full(ncomp, N * M, np.int64)
+            np.minimum.at(first, comp, root_lat)
+            firsts, gid = np.unique(first[comp], return_inverse=True)      # gid: node -> mosaic component, 0-based, in numbering order
+        else:
+            firsts, gid = np.zeros(0, np.int64), np.zeros(0, np.int64)
+        G = int(firsts.size)
+        if G > np.iinfo(np.int32).max:
+            raise RuntimeError("process_depressions: %d depressions do not fit int32 labels" % G)
+        spill = np.zeros(G)
+        spill[gid] = level
+        # 4. the tiles' partial tables: row areas, quanta, owners, halo rings
+        row_area = np.zeros(N)
+        for i in reversed(range(nt)):
+            dp = self.tiles[i]
+            row_area[lat[i, 0]:lat[i, 0] + lat[i, 2]] = np.asarray(dp.dX2, np.float64) * np.asarray(dp.dY2, np.float64)
+        amax = float(row_area.max()) if N else 0.0
+        dmax = max([float(l['max_depth']) for l in local] + [0.0]) if G else 0.0
+        sh_a, q_a = conditioning.fixed_point(N * M, amax)
+        sh_v, q_v = conditioning.fixed_point(N * M, dmax * amax)
+        col = {nm: k for k, nm in enumerate(conditioning.SEAM_TABLE_COLS)}
+        jobs = [None] * nt
+        for i in range(nt):
+            r0, c0, n, m = [int(v) for v in lat[i]]
+            owner = np.ones((n, m), np.uint8)
+            for j in range(i):
+                a0, a1 = max(r0, int(lat[j, 0])), min(r0 + n, int(lat[j, 0] + lat[j, 2]))
+                b0, b1 = max(c0, int(lat[j, 1])), min(c0 + m, int(lat[j, 1] + lat[j, 3]))
+                if a0 < a1 and b0 < b1:
+                    owner[a0 - r0:a1 - r0, b0 - c0:b1 - c0] = 0
+            halo_g = np.full(2 * m + 2 * n + 4, -1, np.int64)        # mosaic component + 1, 0 not raised, -1 no data or uncovered
+            halo_W = np.full(2 * m + 2 * n + 4, np.nan)
+            for k, (start, parts) in enumerate(rings[i]):
+                for mine, j, index, theirs in parts:
+                    b = idl[(j, 0 if k < 2 else 1, index)][theirs].astype(np.int64)
+                    seg = slice(start + mine.start, start + mine.stop)
+                    node = np.minimum(off[j] + np.maximum(b, 1) - 1, max(nn - 1, 0))        # (any valid index where b <= 0)
+                    halo_g[seg] = np.where(b > 0, gid[node] + 1 if nn else 0, b)
+                    halo_W[seg] = Wl[(j, 0 if k < 2 else 1, index)][theirs]
+            mine_g = gid[off[i]:off[i + 1]]
+            rows = np.unique(np.concatenate([mine_g, halo_g[halo_g > 0] - 1]))       # the mosaic components this tile can meet
+            lut = np.zeros(mine_g.size + 1, np.int32)
+            lut[1:] = np.searchsorted(rows, mine_g) + 1
+            halo_ids = np.where(halo_g > 0, np.searchsorted(rows, np.maximum(halo_g, 1) - 1) + 1, halo_g).astype(np.int32)
+            jobs[i] = (rows, lut, owner, halo_ids, halo_W, np.ascontiguousarray(row_area[r0:r0 + n]))
+        part = [None] * nt
+        self._per_tile(lambda i: part.__setitem__(i, self.tiles[i].fill_seam_inventory(jobs[i][1], jobs[i][0].size, jobs[i][2], jobs[i][3],
+                                                                                       jobs[i][4], jobs[i][5], sh_a, sh_v)))
+        ms['inventory'] = sum(p['ms'] for p in part)
+        # 5. combine: sums, and minima / maxima in lattice coordinates (local raster order is monotone in lattice order)
+        big = np.iinfo(np.int64).max
+        cells, n_sills, open_sill = np.zeros(G, np.int64), np.zeros(G, np.int64), np.zeros(G, np.int64)
+        area, volume = np.zeros(G, np.int64), np.zeros(G, np.int64)
+        br0, bc0, bottom, pour = (np.full(G, big, np.int64) for _ in range(4))
+        br1, bc1 = np.full(G, -1, np.int64), np.full(G, -1, np.int64)
+        zmin = np.full(G, ~np.uint64(0), np.uint64)
+        bottom_elev = np.zeros(G)
+        for i in range(nt):
+            rows, t = jobs[i][0], part[i]['table']
+            cells[rows] += t[col['cells']].astype(np.int64)
+            n_sills[rows] += t[col['n_sills']].astype(np.int64)
+            area[rows] += t[col['area']].view(np.int64)
+            volume[rows] += t[col['volume']].view(np.int64)
+            open_sill[rows] = np.maximum(open_sill[rows], t[col['open']].astype(np.int64))
+            zmin[rows] = np.minimum(zmin[rows], t[col['zmin']])
+        for i in range(nt):
+            r0, c0, n, m = [int(v) for v in lat[i]]
+            rows, t = jobs[i][0], part[i]['table']
+            has = t[col['cells']] > 0
+            k = rows[has]
+            br0[k] = np.minimum(br0[k], t[col['r0']][has].astype(np.int64) + r0)
+            br1[k] = np.maximum(br1[k], t[col['r1']][has].astype(np.int64) + r0)
+            bc0[k] = np.minimum(bc0[k], t[col['c0']][has].astype(np.int64) + c0)
+            bc1[k] = np.maximum(bc1[k], t[col['c1']][has].astype(np.int64) + c0)
+            low = has & (t[col['zmin']] == zmin[rows])
+            b = t[col['bottom']][low].astype(np.int64)
+            b = (r0 + b // m) * M + c0 + b % m
+            better = b < bottom[rows[low]]
+            bottom[rows[low][better]] = b[better]
+            bottom_elev[rows[low][better]] = t[col['bottom_elev']][low][better].view(np.float64)
+            sills = t[col['n_sills']] > 0
+            p = t[col['pour']][sills].astype(np.int64)
+            pour[rows[sills]] = np.minimum(pour[rows[sills]], (r0 + p // m) * M + c0 + p % m)
+        if G and ((cells < 1).any() or (n_sills < 1).any() or (bottom >= N * M).any()):
+            raise RuntimeError("process_depressions: a depression without cells, without a bottom or without a sill cell")
+        table = conditioning.depression_table(cells, br0, br1, bc0, bc1, spill, bottom, bottom_elev, pour, n_sills, open_sill,
+                                              area.astype(np.float64) * q_a, volume.astype(np.float64) * q_v, M)
+        keep = (table['max_depth'] >= lim['min_depth']) & (table['cells'] >= lim['min_cells']) & (table['volume'] >= lim['min_volume'])
+        number = np.zeros(G, np.int32)
+        number[keep] = np.arange(1, int(keep.sum()) + 1)
+        # 6. labels
+        labels = None
+        if return_labels:
+            got = [None] * nt
+            luts = [np.concatenate(([0], number[gid[off[i]:off[i + 1]]])).astype(np.int32) for i in range(nt)]
+            self._per_tile(lambda i: got.__setitem__(i, self.tiles[i].fill_seam_labels(luts[i])))
+            ms['labels'] = sum(g['ms'] for g in got)
+            labels = [g['label'] for g in got]
+        return table[keep], labels, dict(n_found=G, quanta=(q_a, q_v), ms=ms)
 
     def _patch_overlap1_edges(self):
         """Single-pixel-overlap fix of the reference's calc_uca worker (:102-180): an edge cell whose
