@@ -128,6 +128,12 @@ int pydem_hip_device_memory(int device, int64_t *free_bytes, int64_t *total_byte
  * the reference (host arrays). */
 int pydem_hip_release_scratch(void);
 
+/* PYDEM_MEM_POISON=<0..255> (read at every hand-out) fills every device block the library hands out -- planes off the free
+ * lists or mapped anew, scratch blocks, the whole conditioning arena at the start of a lease -- with that byte before the
+ * pointer is used: a debug mode that makes "whatever the last owner left" a known pattern.  This returns the process totals
+ * of what was filled (0, 0 while the variable has never been set). */
+int pydem_hip_poison_stats(int64_t *blocks, int64_t *bytes);
+
 int pydem_tile_create(int64_t n_rows, int64_t n_cols, int device, pydem_tile **out);
 int pydem_tile_destroy(pydem_tile *t);
 /* dX, dY: n_rows-1 values; dX2, dY2: n_rows values (DEMProcessor.__init__ :229-258) */

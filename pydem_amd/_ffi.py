@@ -53,6 +53,7 @@ SYMBOLS = {
     'pydem_hip_device_count': (C.c_int, [C.POINTER(C.c_int)]),
     'pydem_hip_device_memory': (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_hip_release_scratch': (C.c_int, []),
+    'pydem_hip_poison_stats': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pydem_hip_device_name': (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     'pydem_tile_create': (C.c_int, [C.c_int64, C.c_int64, C.c_int, _PP]),
     'pydem_tile_destroy': (C.c_int, [_P]),
@@ -190,6 +191,13 @@ def device_count():
 def release_scratch():
     """Return the per-device scratch arenas of the conditioning stages to the driver."""
     check(load().pydem_hip_release_scratch())
+
+
+def poison_stats():
+    """(blocks, bytes) of device memory that PYDEM_MEM_POISON has filled at hand-out in this process."""
+    n, b = C.c_int64(0), C.c_int64(0)
+    check(load().pydem_hip_poison_stats(C.byref(n), C.byref(b)))
+    return n.value, b.value
 
 
 def device_memory(device=0):

@@ -590,8 +590,10 @@ int pydem_board_create(int device, int n_tiles, int64_t n_doubles, pydem_board *
     HIP_TRY(hipEventCreateWithFlags(&b->ev, hipEventDisableTiming));
     HIP_TRY(dev_malloc((void **)&b->mb, (size_t)(n_doubles > 0 ? n_doubles : 1) * 8));
     HIP_TRY(hipMemsetAsync(b->mb, 0, (size_t)(n_doubles > 0 ? n_doubles : 1) * 8, b->stream));
-    HIP_TRY(hipMalloc((void **)&b->desc, (size_t)n_tiles * sizeof(pydem_board_desc)));
-    HIP_TRY(hipMalloc((void **)&b->scal, (size_t)n_tiles * 8 * sizeof(unsigned long long)));
+    HIP_TRY(dev_malloc((void **)&b->desc, (size_t)n_tiles * sizeof(pydem_board_desc)));
+    HIP_TRY(dev_malloc((void **)&b->scal, (size_t)n_tiles * 8 * sizeof(unsigned long long)));
+    // (pydem_board_eval returns the rows of ALL tiles, "previous values" for those it was not asked about: zero before the first look)
+    HIP_TRY(hipMemsetAsync(b->scal, 0, (size_t)n_tiles * 8 * sizeof(unsigned long long), b->stream));
     HIP_TRY(hipHostMalloc((void **)&b->h_scal, (size_t)n_tiles * 8 * sizeof(unsigned long long)));
     b->h_desc.resize((size_t)n_tiles);
     *out = b;
@@ -696,7 +698,7 @@ int pydem_board_set_lines(pydem_board *b, int index, int64_t mb_start, int64_t s
     }
     dev_free(T.lines);
     T.lines = nullptr;
-    HIP_TRY(hipMalloc((void **)&T.lines, (size_t)(count > 0 ? count : 1) * sizeof(pydem_pack_line)));
+    HIP_TRY(dev_malloc((void **)&T.lines, (size_t)(count > 0 ? count : 1) * sizeof(pydem_pack_line)));
     HIP_TRY(hipMemcpyAsync(T.lines, h.data(), (size_t)count * sizeof(pydem_pack_line), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     T.count = count;
@@ -840,9 +842,9 @@ static int board_prepare(pydem_board *b, bool staged, unsigned long long ok)
     if ((int)b->tl.size() != b->n_tiles) { pydem_set_error("pydem_board_run_waves: pydem_board_set_lines first"); return -2; }
     b->prepared = false;
     if (!b->sched) {
-        HIP_TRY(hipMalloc((void **)&b->sched, SCH_WORDS * sizeof(unsigned long long)));
+        HIP_TRY(dev_malloc((void **)&b->sched, SCH_WORDS * sizeof(unsigned long long)));
         HIP_TRY(hipHostMalloc((void **)&b->h_sched, SCH_WORDS * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc((void **)&b->scal_tb, 64 * 8 * sizeof(unsigned long long)));
+        HIP_TRY(dev_malloc((void **)&b->scal_tb, 64 * 8 * sizeof(unsigned long long)));
         HIP_TRY(hipHostMalloc((void **)&b->h_progress, 2 * sizeof(unsigned long long)));
         b->h_progress[0] = b->h_progress[1] = 0;
     }
@@ -912,15 +914,15 @@ static int board_prepare(pydem_board *b, bool staged, unsigned long long ok)
         }
         b->q_count = (int)mine.size(); b->q_nlines = (int)hl.size(); b->q_nunpack = (int)hu.size();
         if (b->q_count) {
-            HIP_TRY(hipMalloc(&b->q_tiles, hq.size()));
+            HIP_TRY(dev_malloc(&b->q_tiles, hq.size()));
             HIP_TRY(hipMemcpy(b->q_tiles, hq.data(), hq.size(), hipMemcpyHostToDevice));
         }
         if (b->q_nlines) {
-            HIP_TRY(hipMalloc(&b->q_lines, hl.size() * sizeof(pydem_pack_line_q)));
+            HIP_TRY(dev_malloc(&b->q_lines, hl.size() * sizeof(pydem_pack_line_q)));
             HIP_TRY(hipMemcpy(b->q_lines, hl.data(), hl.size() * sizeof(pydem_pack_line_q), hipMemcpyHostToDevice));
         }
         if (b->q_nunpack) {
-            HIP_TRY(hipMalloc(&b->q_unpack, hu.size() * sizeof(pydem_unpack_line)));
+            HIP_TRY(dev_malloc(&b->q_unpack, hu.size() * sizeof(pydem_unpack_line)));
             HIP_TRY(hipMemcpy(b->q_unpack, hu.data(), hu.size() * sizeof(pydem_unpack_line), hipMemcpyHostToDevice));
         }
         b->tables_valid = true; b->wave_ok = ok;

@@ -1,10 +1,12 @@
 // devmem.hip -- where the library's device and pinned memory comes from: the plane cache, dev_malloc / dev_free, the per-device
 // scratch arena, the tile's pinned staging and the threaded whole-plane transfers.  What a tile holds is kept by tile_mem.h.
 #include "internal.h"
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
+#include <stdlib.h>
 #include <string.h>
 #include <time.h>
 #include <sys/mman.h>
@@ -59,6 +61,32 @@ void plane_cache_evict(PlaneCache *c, size_t room, std::vector<void *> &victims)
     }
 }
 constexpr size_t PLANE_MIN = (size_t)1 << 20;
+
+// ---- PYDEM_MEM_POISON=<0..255>: a debug mode that makes "whatever the last owner left" a known byte --------------------
+// Read at every hand-out (like PYDEM_STENCIL_SPLIT per launch: a test switches it between calls), never cached.  When it is
+// set, every device block this file hands out -- a plane off the free list or mapped anew, a dev_malloc block, the whole arena
+// at the start of a lease -- is filled with that byte, and the device is idle again before the pointer is returned.  Unset (or
+// not a number in 0..255): nothing happens.  pydem_hip_poison_stats reports how much was filled.
+std::atomic<int64_t> g_poison_blocks{0}, g_poison_bytes{0};
+int poison_byte()
+{
+    const char *e = getenv("PYDEM_MEM_POISON");
+    if (!e || !*e) return -1;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 0);
+    return (end == e || *end || v < 0 || v > 255) ? -1 : (int)v;
+}
+// `drain_first`: work of an earlier owner may still run on some stream of the device (the arena: the previous lease's stage
+// ran on a tile stream)
+void poison(void *p, size_t bytes, bool drain_first = false)
+{
+    const int v = poison_byte();
+    if (v < 0 || !p || !bytes) return;
+    if (drain_first) (void)hipDeviceSynchronize();
+    (void)hipMemset(p, v, bytes);
+    (void)hipDeviceSynchronize();
+    g_poison_blocks += 1; g_poison_bytes += (int64_t)bytes;
+}
 void plane_cache_flush(int device)
 {
     PlaneCache *c = plane_cache(device);
@@ -79,6 +107,7 @@ void *plane_take(int device, size_t bytes)
             void *q = it->second.p;
             c->free_blocks.erase(it); c->kept -= bytes;
             c->live[q] = bytes;
+            poison(q, bytes);
             return q;
         }
         // (a size the lists do not hold: nothing is evicted here -- the blocks on the lists are those of the tile destroyed
@@ -105,6 +134,7 @@ void *plane_take(int device, size_t bytes)
         std::lock_guard<std::mutex> g(c->mu);
         c->live[q] = bytes;
     }
+    poison(q, bytes);
     return q;
 }
 
@@ -141,7 +171,15 @@ hipError_t dev_malloc(void **p, size_t bytes)
         (void)hipGetLastError();
         if (hipGetDevice(&device) == hipSuccess) { plane_cache_flush(device); e = hipMalloc(p, bytes); }
     }
+    if (e == hipSuccess) poison(*p, bytes);
     return e;
+}
+
+int pydem_hip_poison_stats(int64_t *blocks, int64_t *bytes)
+{
+    if (blocks) *blocks = g_poison_blocks.load();
+    if (bytes) *bytes = g_poison_bytes.load();
+    return 0;
 }
 
 void dev_free(void *p) { if (p) (void)hipFree(p); }
@@ -165,6 +203,7 @@ int arena_acquire(int device, ArenaLease *L)
     DevArena *a = arena_of(device);
     a->busy.lock();
     L->device = device; L->arena = a; L->base = (char *)a->p; L->bytes = a->bytes; L->off = 0; L->want = 0; L->held = true;
+    poison(a->p, a->bytes, true);       // (the lease starts empty: nothing the arena holds means anything)
     return 0;
 }
 
