@@ -1115,7 +1115,9 @@ __global__ __launch_bounds__(64 * LWPB, PYDEM_LISTED_OCC) void k_sweep_tiles_lis
 // < p: one lane per cell, no lists, no atomics besides the count, the same gather order as the tile visits (NW ... SE,
 // then the pit in-edges by source), so the values are bit-identical to theirs.  A stamp of THIS level reads as "open"
 // (levels < p count), so concurrent stamps never let a cell read a value written in the same launch.
+// (WT: seed per cell, signed shares, no taint -- see sweep_one_tile)
 constexpr int DENSE_BAND = 64;
+template <bool WT = false>
 __global__ __launch_bounds__(256) void k_sweep_dense_level(SweepArgs A, uint32_t p, int32_t *n_final)
 {
     const int n = A.n, m = A.m;
@@ -1149,16 +1151,20 @@ __global__ __launch_bounds__(256) void k_sweep_dense_level(SweepArgs A, uint32_t
             }
             if (!ready) continue;
         }
-        double a = A.a0[i];
-        bool td = (i == 0 || i == n - 1 || j == 0 || j == m - 1) && A.todo_work[c] != 0;
+        double a = WT ? A.a0[c] : A.a0[i];
+        bool td = !WT && (i == 0 || i == n - 1 || j == 0 || j == m - 1) && A.todo_work[c] != 0;
 #pragma unroll
         for (int d = 0; d < 8; d++)
-            if (cw & (1u << d)) { const double x = in_edge(A, c, m, d); a += fabs(x); td = td || (x < 0); }
+            if (cw & (1u << d)) {
+                const double x = in_edge(A, c, m, d);
+                if constexpr (WT) a += x;
+                else { a += fabs(x); td = td || (x < 0); }
+            }
         if (cw & CI_PIT_IN)
             for (int32_t e = po.x; e < A.n_pit && A.pin_dst[e] == c; e++) {
                 const int32_t sc = A.pin_src[e];
                 a += A.area[sc] * A.pin_w[e];
-                td = td || (A.todo_work[sc] != 0);
+                if constexpr (!WT) td = td || (A.todo_work[sc] != 0);
             }
         double2 o = make_double2(0.0, 0.0);
         if (cw & (CI_OUT1 | CI_OUT2)) {
@@ -1455,7 +1461,8 @@ __global__ __launch_bounds__(64) void k_sweep_tiles_resident(SweepArgs A, uint32
 // owner sees the zero in the next round).  At the end the rows of the tile are written once, coalesced: contribution
 // 16 B + graph word 4 B per finished cell; the generic pass stored them in dependency order and paid ~47 B of write
 // traffic per finished cell for 28 (profiles/README.md).  Cells with pit edges, cells fed from another tile and
-// everything downstream of them are left to pass 2.
+// everything downstream of them are left to pass 2.  (WT: the seed of a cell comes from global memory when the cell is finished,
+// signed shares, no taint -- see sweep_one_tile)
 constexpr uint32_t FC_COUNT = 0xFu, FC_BLOCKED = 1u << 8, FC_DONE = 1u << 9, FC_TODO = 1u << 10;   // low half of the cell word
 
 struct TileFirst {
@@ -1472,6 +1479,7 @@ __device__ __forceinline__ void lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+template <bool WT = false>
 __global__ __launch_bounds__(256) void k_sweep_first(SweepArgs A, int tiles_x, int tiles_total, uint8_t *__restrict__ tile_done,
                                                      int32_t *n_final)
 {
@@ -1500,7 +1508,7 @@ __global__ __launch_bounds__(256) void k_sweep_first(SweepArgs A, int tiles_x, i
             cw[k] = ok ? A.cinfo[c] : 0xFFFFFFFFu;
             pv[k] = ok ? A.prop[c] : 0.0;
         }
-        if (t < TT) L.a0[t] = (i0 + t < n) ? A.a0[i0 + t] : 0.0;
+        if (t < TT) L.a0[t] = (!WT && i0 + t < n) ? A.a0[i0 + t] : 0.0;
         const uint32_t out_col = (l32 == 0 ? 0x29u : 0u) | (l32 == TT - 1 ? 0x94u : 0u);      // in-edges that would come from another tile
         const bool edge_col = gj == 0 || gj == m - 1;
 #pragma unroll
@@ -1513,7 +1521,7 @@ __global__ __launch_bounds__(256) void k_sweep_first(SweepArgs A, int tiles_x, i
                 const uint32_t outside = out_col | (r == 0 ? 0x07u : 0u) | (r == TT - 1 ? 0xE0u : 0u);
                 const bool blocked = ((w & 0xFFu & outside) != 0u) || (w & (CI_PIT_IN | CI_PIT_OUT));
                 word = ((w & CI_STATIC_MASK) << 16) | __popc(w & 0xFFu) | (blocked ? FC_BLOCKED : 0u);
-                if (!blocked && (edge_col || gi == 0 || gi == n - 1) && A.todo_work[(int64_t)gi * m + gj] != 0) word |= FC_TODO;   // inlet cells of the tile's edge
+                if (!WT && !blocked && (edge_col || gi == 0 || gi == n - 1) && A.todo_work[(int64_t)gi * m + gj] != 0) word |= FC_TODO;   // inlet cells of the tile's edge
             }
             L.cs[t + 256 * k] = word;
             L.slot[t + 256 * k].x = pv[k];
@@ -1542,7 +1550,7 @@ __global__ __launch_bounds__(256) void k_sweep_first(SweepArgs A, int tiles_x, i
                 const int r = cur >> 5, cl = cur & 31;
                 const uint32_t word = L.cs[cur], w = word >> 16;
                 const double pv = L.slot[cur].x;
-                double a = L.a0[r];
+                double a = WT ? A.a0[(int64_t)(i0 + r) * m + j0 + cl] : L.a0[r];
                 bool td = (word & FC_TODO) != 0u;
                 uint32_t mm = w & 0xFFu;
                 while (mm) {                                        // ascending neighbour order, like the reference's pull
@@ -1550,7 +1558,8 @@ __global__ __launch_bounds__(256) void k_sweep_first(SweepArgs A, int tiles_x, i
                     const int q = d + (d >> 2), di = (q * 11) >> 5;            // q = 0..8 with the centre skipped, di = q / 3
                     const double2 u = L.slot[cur + (di - 1) * TT + (q - 3 * di - 1)];
                     const double x = ((0x5A >> d) & 1) ? u.x : u.y;             // cardinal neighbours hand over their first share
-                    a += fabs(x); td = td || (x < 0);
+                    if constexpr (WT) a += x;
+                    else { a += fabs(x); td = td || (x < 0); }
                 }
                 double2 o = make_double2(0.0, 0.0);
                 if (w & CI_OUT1) o.x = a * pv;
@@ -2155,7 +2164,7 @@ static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
             if (hipStreamSynchronize(t->stream) != hipSuccess) return -1;
             ntiles = t->h_counters[CS_TILE_LIST + p % 3];
             listed_left = ntiles;
-            if (getenv("PYDEM_SWEEP_DEBUG")) fprintf(stderr, "listed tile pass %d: %lld tiles listed next, processed %d\n", p, (long long)ntiles, t->h_counters[CS_PROCESSED]);
+            if (getenv("PYDEM_SWEEP_DEBUG")) fprintf(stderr, "listed tile pass %d: %lld tiles listed next, processed %d (%d %s passes)\n", p, (long long)ntiles, t->h_counters[CS_PROCESSED], batch, resident ? "resident" : "generic");
             if (p > (int)CI_LEVEL_INF - 256) return -2;
         }
         return p;
@@ -2272,14 +2281,14 @@ static int sweep_schedule(pydem_tile *t, const pydem_options *opt, double *seed)
         // the default (profiles/r04_sweep_passes_dense*.txt)
         static int dense_levels = -1;
         if (dense_levels < 0) { const char *e = getenv("PYDEM_SWEEP_DENSE"); dense_levels = e ? atoi(e) : 0; if (dense_levels < 0) dense_levels = 0; }
-        for (int lv = 1; !WT && lv <= dense_levels; lv++) {
-            hipLaunchKernelGGL(k_sweep_dense_level, dim3((unsigned)cdiv(m, 256), (unsigned)cdiv(n, DENSE_BAND)), dim3(256), 0, t->stream,
+        for (int lv = 1; lv <= dense_levels; lv++) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_dense_level<WT>), dim3((unsigned)cdiv(m, 256), (unsigned)cdiv(n, DENSE_BAND)), dim3(256), 0, t->stream,
                                A, (uint32_t)lv, total);
             launches++;
         }
-        const uint32_t pb = WT ? 0u : (uint32_t)dense_levels;       // passes so far
-        if (!WT && first_kind == 1 && TH == 32 && pb == 0)
-            hipLaunchKernelGGL(k_sweep_first, dim3((unsigned)(((tiles_total + 7) / 8) * 8)), dim3(256), 0, t->stream, A, tiles_x, tiles_total, tile_done, total);
+        const uint32_t pb = (uint32_t)dense_levels;       // passes so far
+        if (first_kind == 1 && TH == 32 && pb == 0)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_first<WT>), dim3((unsigned)(((tiles_total + 7) / 8) * 8)), dim3(256), 0, t->stream, A, tiles_x, tiles_total, tile_done, total);
         else {
             TileNext N0; N0.flag = nullptr; N0.list = nullptr; N0.count = nullptr;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_tiles<false, WT>), dim3(full_grid), dim3(64 * FWPB), (size_t)lds_pad, t->stream, A, pb + 1u, tiles_x, tiles_total, tile_done, total, N0, work16);

@@ -11,6 +11,14 @@ here isolates one of those:
     near_pit     one pit at a tile corner with drains in the three other tiles around the corner
     tall, wide   chains longer than the row kernels' grid (more than 4096 rows) and than one workgroup's 256 columns
 
+and for the UCA sweep (csrc/uca.hip, tests/test_gpu_uca_fields.py), whose edge taint reaches every cell of the fields above:
+
+    roof(kl, kr) two fans side by side that flow apart: only one of the top and bottom rows is an inlet row, so the taint
+                 covers part of the grid and part of most 32-blocks
+    tile_snake_wide        tile_snake over five blocks of columns: two of them are wholly open after the two full passes
+    tall_long, wide_long   tall and wide with a side of 16500: past the 16384 rows / 64 x 256 columns of the capped launches
+    strip        a 16500 x 5 or 5 x 16500 fractal tile, slopes computed: the same caps with flats, pits and every section
+
 A field is a `Field`: the elevation, the spacing, the options of OracleDEM / DEMProcessor, mag / direction / flats where the
 field is hand-made (None: the slopes are computed), the target of the downslope calls and `facts`, what the tests assert
 about it.  Hand-made fields take drain_pits=False and dX = 2, dY = 3; so do the computed ones unless they say otherwise.
@@ -79,7 +87,7 @@ def row_snake(n=70, m=45):
 
 
 @functools.lru_cache(maxsize=None)
-def tile_snake(n=40, m=70):
+def tile_snake(n=40, m=70, name='tile_snake'):
     """A column snake inside each 32-block (down column 0, up column 1, ...), which leaves the block at the top of its last
     column for the block to the east; one chain per tile row.  Every block, the ragged ones included, needs an even number
     of columns for that."""
@@ -93,9 +101,15 @@ def tile_snake(n=40, m=70):
             for j in cols:
                 path += [(i, j) for i in (rows if (j - j0) % 2 == 0 else rows[::-1])]
         paths.append(path)
-    f = _from_paths('tile_snake', (n, m), paths, last=E)
+    f = _from_paths(name, (n, m), paths, last=E)
     f.facts['longest_run'] = longest_run_in_one_block(f.facts['path'])
     return f
+
+
+def tile_snake_wide():
+    """tile_snake over five blocks of columns: the first two full passes of the UCA sweep finish one block each, so the third
+    and fourth block are open in all their 1024 cells when the pass after them visits them"""
+    return tile_snake(40, 134, 'tile_snake_wide')
 
 
 @functools.lru_cache(maxsize=None)
@@ -160,17 +174,73 @@ def near_pit():
 
 
 @functools.lru_cache(maxsize=None)
-def tall(n=4100, m=3):
+def tall(n=4100, m=3, name='tall'):
     """Every column flows south: chains of n cells, more rows than the grid of the row kernels has workgroups (4096)."""
     paths = [[(i, j) for i in range(n)] for j in (1, 0, 2)]            # (the middle column first: `path` is that one)
-    return _from_paths('tall', (n, m), paths, last=S)
+    return _from_paths(name, (n, m), paths, last=S)
 
 
 @functools.lru_cache(maxsize=None)
-def wide(n=3, m=700):
+def wide(n=3, m=700, name='wide'):
     """Every row flows west: chains of m cells over three workgroups of the row kernels (256 columns each)."""
     paths = [[(i, j) for j in range(m - 1, -1, -1)] for i in (1, 0, 2)]
-    return _from_paths('wide', (n, m), paths, last=W)
+    return _from_paths(name, (n, m), paths, last=W)
+
+
+LONG = 16500            # more rows than the row and column kernels of csrc/uca.hip have workgroups (16384) or threads
+
+
+def tall_long():
+    """tall with 16500 rows: the grid-stride branch of every kernel whose grid is capped at 16384 rows"""
+    return tall(LONG, 3, 'tall_long')
+
+
+def wide_long():
+    """wide with 16500 columns: 65 workgroups of 256 columns where the capped launches have 64"""
+    return wide(3, LONG, 'wide_long')
+
+
+@functools.lru_cache(maxsize=None)
+def roof(kl, kr, n=70, m=90):
+    """Two fans side by side: the columns left of m // 2 take the uniform direction (kl + 0.3) pi / 4, the others
+    (kr + 0.3) pi / 4, each half on the plane of `fan` that falls along its direction.  With (kl, kr) = (3, 0) or (4, 7) the
+    halves flow apart, no edge crosses the ridge, and only the bottom (top) row is an inlet row: the edge taint spreads over
+    part of the grid only."""
+    sp = _spacing()
+    ii, jj = np.indices((n, m))
+    x, y = jj * sp['dX'], -ii * sp['dY']
+    left = jj < m // 2
+    direction = np.where(left, (kl + 0.3) * np.pi / 4, (kr + 0.3) * np.pi / 4)
+    elev = 1000.0 - (x * np.cos(direction) + y * np.sin(direction))
+    e1 = [(0, 1), (-1, 0), (-1, 0), (0, -1), (0, -1), (1, 0), (1, 0), (0, 1)]
+    e2 = [(-1, 1), (-1, 1), (-1, -1), (-1, -1), (1, -1), (1, -1), (1, 1), (1, 1)]
+    target = np.zeros((n, m), bool)
+    for half, k in ((left, kl), (~left, kr)):
+        for di, dj in (e1[k], e2[k]):
+            target |= half & ((ii + di < 0) | (ii + di >= n) | (jj + dj < 0) | (jj + dj >= m))
+    return Field('roof%d%d' % (kl, kr), elev, sp, dict(drain_pits=False), np.ones((n, m)), direction, np.zeros((n, m), bool), target,
+                 dict(sections=(kl, kr), ridge=m // 2))
+
+
+@functools.lru_cache(maxsize=None)
+def strip(shape, seed=61):
+    """A fractal tile five cells across and 16500 long, slopes computed, pits drained: flats, pits and every facet section
+    where one side is longer than the capped grids of the row, column and line-gather kernels."""
+    from pydem_amd import synth
+    elev = synth.fractal(shape[0], shape[1], seed=seed, top_shift=7, n_octaves=7)
+    return Field('strip_%dx%d' % shape, elev, dict(dX=30.0, dY=30.0), dict(drain_pits=True), None, None, None, None, dict(seed=seed))
+
+
+def blocks_mixed(mask):
+    """(32-blocks that hold both True and False cells of `mask`, all 32-blocks)"""
+    n, m = mask.shape
+    mixed = total = 0
+    for i0 in range(0, n, T):
+        for j0 in range(0, m, T):
+            b = mask[i0:i0 + T, j0:j0 + T]
+            total += 1
+            mixed += bool(b.any() and not b.all())
+    return mixed, total
 
 
 def oracle(field):

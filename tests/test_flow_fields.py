@@ -1,6 +1,8 @@
 """CPU tier: what each designed field of tests/flow_fields.py is on the oracle's graph, so that tests/test_gpu_flow_fields.py
 cannot go vacuous: the chains and their depth under the three references (dist_down_ref, dist_up_ref, rev_accum_ref), the
-single section and the two unequal out-edges of the fans, where the pits drain, and the closed forms the device is held to."""
+single section and the two unequal out-edges of the fans, where the pits drain, and the closed forms the device is held to.
+The fields made for the UCA sweep (tests/test_gpu_uca_fields.py) follow: uca along the chains, the partly tainted roofs, the
+chains and strips longer than the capped grids."""
 import functools
 
 import numpy as np
@@ -130,3 +132,65 @@ def test_near_pit_drains_round_a_tile_corner():
     assert divmod(pit, m) == (30, 30) and o.n_warn == 0
     blocks = set(zip((dst // m // F.T).tolist(), (dst % m // F.T).tolist()))
     assert (0, 0) not in blocks and len(blocks) == 3
+
+
+# ---- the fields of the UCA sweep (tests/test_gpu_uca_fields.py)
+CHAINS = SNAKES + ('tall_long', 'wide_long', 'tile_snake_wide')
+
+
+@pytest.mark.parametrize('name', CHAINS)
+def test_uca_along_the_chains_is_a_running_count(name):
+    """every cell area is 2 * 3 and every edge weight 1: uca along a path is 6, 12, 18, ... exactly, whatever the order of
+    the additions; and the taint reaches every cell of these fields (no cell is done)"""
+    f = getattr(F, name)()
+    o = oracle(name)
+    assert f.name == name and (o.A[2] == 1.0).all()
+    for p in f.facts['paths']:
+        want = np.cumsum((o.dX2 * o.dY2)[p[:, 0]])
+        assert np.array_equal(want, 6.0 * np.arange(1, len(p) + 1))
+        assert np.array_equal(o.uca[p[:, 0], p[:, 1]], want)
+    assert o.edge_done.sum() == 0
+
+
+def test_the_long_chains_pass_the_capped_grids():
+    assert F.tall_long().elev.shape == (16500, 3) and F.wide_long().elev.shape == (3, 16500)
+    assert F.LONG > 16384 and -(-F.LONG // 256) > 64
+    assert F.tall_long().facts['crossings'] == F.wide_long().facts['crossings'] == 515
+    assert F.tall_long().facts['depth'] == F.wide_long().facts['depth'] == F.LONG
+    # the wide tile snake: four whole blocks of columns and a ragged one, one crossing from block to block
+    f = F.tile_snake_wide()
+    assert f.elev.shape == (40, 134) and f.facts['crossings'] == 4 and f.facts['longest_run'] == 1024
+    assert f.facts['depth'] == 32 * 134
+
+
+@pytest.mark.parametrize('kl,kr', [(3, 0), (4, 7)])
+def test_roofs_are_partly_tainted(kl, kr):
+    f = F.roof(kl, kr)
+    o = oracle('roof', kl, kr)
+    n, m = f.elev.shape
+    assert (n, m) == (70, 90) and f.name == 'roof%d%d' % (kl, kr)
+    # one section per half, two unequal out-edges per cell, no edge across the ridge
+    r = f.facts['ridge']
+    assert np.array_equal(np.unique(o.section[:, :r]), [kl]) and np.array_equal(np.unique(o.section[:, r:]), [kr])
+    od = F.out_degree(o)
+    assert (od == 2).mean() >= 0.90 and np.array_equal(f.target, od < 2) and np.abs(o.A[2] - 0.5).min() > 0.05
+    indptr, indices, _ = o.A
+    src = np.repeat(np.arange(n * m), np.diff(indptr))
+    assert ((src % m < r) == (indices % m < r)).all()
+    # only one of the top and bottom rows takes flow from outside: the taint stops short of most of the grid
+    todo, done = o.edge_todo.astype(bool), o.edge_done.astype(bool)
+    assert todo.sum() == 88 and (todo[0].any() != todo[-1].any()) and not todo[1:-1].any()
+    assert 0.4 <= done.mean() <= 0.8 and done.sum() == 4230
+    mixed, total = F.blocks_mixed(done)
+    assert total == 9 and mixed >= 5
+    assert not np.isnan(o.uca).any()
+
+
+@pytest.mark.parametrize('shape', [(16500, 5), (5, 16500)])
+def test_strips_hold_pits_flats_and_every_section(shape):
+    f = F.strip(shape)
+    o = oracle('strip', shape)
+    assert f.elev.shape == shape and f.name == 'strip_%dx%d' % shape and max(shape) > 16384
+    assert len(np.unique(o.pit_i)) >= 100 and o.flats.any()
+    assert set(range(8)) <= set(np.unique(o.section).tolist())
+    assert 0.1 <= o.edge_done.astype(bool).mean() <= 0.9
