@@ -57,6 +57,9 @@ def lib():
         L.oracle_uca_chunk.argtypes = [_f64p, _i8p, _u8p, C.c_int64, C.c_int64, _f64p, _f64p,
                                        _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_double,
                                        _f64p, _u8p, _u8p, _f64p]
+        L.oracle_uca_init.restype = C.c_double
+        L.oracle_uca_init.argtypes = [_f64p, _i8p, C.c_int64, C.c_int64, _f64p, _f64p, _i32p, _i32p, _f64p,
+                                      _f64p, _u8p, _f64p, _f64p, _u8p]
         L.oracle_uca_update.argtypes = [_f64p, _u8p, C.c_int64, C.c_int64, _i32p, _i32p, _f64p,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         _f64p, _u8p, _u8p]
@@ -242,6 +245,18 @@ class OracleDEM(object):
         else:
             self.pit_i = self.pit_j = self.pit_prop = None
         self.A = adjacency(self.section, self.proportion, self.elev, self.pit_i, self.pit_j, self.pit_prop)
+
+    def uca_drain_state(self):
+        """After build_graph: the state with which _calc_uca_chunk enters its drain loop (:882-945), flat arrays:
+        dict(area, ids (also the initial done), edge_todo, edge_todo_no_mask (the taints, float64), edge_todo_i)."""
+        n, m = self.elev.shape
+        indptr, indices, data = self.A
+        idx = indices if indices.size else np.zeros(1, np.int32)
+        dat = data if data.size else np.zeros(1)
+        area = np.empty(n * m); et = np.empty(n * m); etnm = np.empty(n * m)
+        ids = np.empty(n * m, np.uint8); todo_i = np.empty(n * m, np.uint8)
+        lib().oracle_uca_init(self.elev, self.section, n, m, self.dX2, self.dY2, indptr, idx, dat, area, ids, et, etnm, todo_i)
+        return dict(area=area, ids=ids.astype(bool), edge_todo=et, edge_todo_no_mask=etnm, edge_todo_i=todo_i.astype(bool))
 
     def calc_uca(self):
         if self.direction is None:

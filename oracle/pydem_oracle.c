@@ -725,22 +725,17 @@ int64_t oracle_drain_connections(uint8_t *arr, uint8_t *ids, const int32_t *indp
  * ---------------------------------------------------------------------------------------- */
 static int isin4(int v, int a, int b, int c, int d) { return v == a || v == b || v == c || v == d; }
 
-int oracle_uca_chunk(const double *elev, const int8_t *section, const uint8_t *flats,
-                     int64_t n, int64_t m, const double *dX2, const double *dY2,
-                     const int32_t *A_indptr, const int32_t *A_indices, const double *A_data,
-                     int64_t circular_ref_maxcount, int apply_uca_limit_edges, double uca_saturation_limit,
-                     double *uca, uint8_t *edge_todo_i, uint8_t *edge_done, double *stats)
+/* The state with which _calc_uca_chunk enters its drain loop (:882-945): ids (= done: the cells without in-edges), the cell
+ * areas, the taints edge_todo / edge_todo_no_mask as doubles and the initial inlet edges (:937).  Returns min_area (:898). */
+double oracle_uca_init(const double *elev, const int8_t *section, int64_t n, int64_t m, const double *dX2, const double *dY2,
+                       const int32_t *A_indptr, const int32_t *A_indices, const double *A_data,
+                       double *area, uint8_t *ids, double *et, double *etnm, uint8_t *edge_todo_i)
 {
-    int64_t NN = n * m, nnz = A_indptr[NN];
-    int32_t *B_indptr = (int32_t *)malloc((NN + 1) * sizeof(int32_t));
-    int32_t *B_indices = (int32_t *)malloc((nnz + 1) * sizeof(int32_t));
-    oracle_tocsr(A_indptr, A_indices, NN, B_indptr, B_indices);          /* :879 */
+    int64_t NN = n * m;
     double *insum = (double *)calloc(NN, sizeof(double));                 /* A.sum(1) :882 */
     for (int64_t c = 0; c < NN; c++)
         for (int32_t k = A_indptr[c]; k < A_indptr[c + 1]; k++) insum[A_indices[k]] += A_data[k];
-    uint8_t *ids = (uint8_t *)malloc(NN), *done = (uint8_t *)malloc(NN);
-    for (int64_t c = 0; c < NN; c++) { ids[c] = (insum[c] == 0); done[c] = ids[c]; }   /* :883, :903-904 */
-    double *area = uca;
+    for (int64_t c = 0; c < NN; c++) { ids[c] = (insum[c] == 0); }   /* :883, :903-904 */
     double min_area = INFINITY;
     for (int64_t i = 0; i < n; i++) {
         double a = dX2[i] * dY2[i];                                        /* :885 */
@@ -774,13 +769,31 @@ int oracle_uca_chunk(const double *elev, const int8_t *section, const uint8_t *f
         }
     }
 #undef OUTSUM
-    double *et = (double *)malloc(NN * sizeof(double)), *etnm = (double *)malloc(NN * sizeof(double));
     for (int64_t c = 0; c < NN; c++) {
         etnm[c] = todo[c];                                                  /* :933-934, :945 */
         if (isnan(elev[c])) todo[c] = 0;                                    /* :935 */
         edge_todo_i[c] = todo[c];                                           /* :937 */
         et[c] = todo[c];                                                    /* :944 */
     }
+    free(insum); free(todo);
+    return min_area;
+}
+
+int oracle_uca_chunk(const double *elev, const int8_t *section, const uint8_t *flats,
+                     int64_t n, int64_t m, const double *dX2, const double *dY2,
+                     const int32_t *A_indptr, const int32_t *A_indices, const double *A_data,
+                     int64_t circular_ref_maxcount, int apply_uca_limit_edges, double uca_saturation_limit,
+                     double *uca, uint8_t *edge_todo_i, uint8_t *edge_done, double *stats)
+{
+    int64_t NN = n * m, nnz = A_indptr[NN];
+    int32_t *B_indptr = (int32_t *)malloc((NN + 1) * sizeof(int32_t));
+    int32_t *B_indices = (int32_t *)malloc((nnz + 1) * sizeof(int32_t));
+    oracle_tocsr(A_indptr, A_indices, NN, B_indptr, B_indices);          /* :879 */
+    uint8_t *ids = (uint8_t *)malloc(NN), *done = (uint8_t *)malloc(NN);
+    double *area = uca;
+    double *et = (double *)malloc(NN * sizeof(double)), *etnm = (double *)malloc(NN * sizeof(double));
+    double min_area = oracle_uca_init(elev, section, n, m, dX2, dY2, A_indptr, A_indices, A_data, area, ids, et, etnm, edge_todo_i);
+    memcpy(done, ids, NN);                                                  /* :903-904 */
     int64_t count = 1, done_sum = 0, calls = 0, rounds = 0;                 /* :939-950 */
     for (;;) {
         int64_t ds = 0, any_undone = 0;
@@ -813,7 +826,7 @@ int oracle_uca_chunk(const double *elev, const int8_t *section, const uint8_t *f
         if (apply_uca_limit_edges && area[c] > uca_saturation_limit * 2 * min_area) edge_done[c] = 1; /* :977-980 */
     }
     if (stats) { stats[0] = (double)calls; stats[1] = (double)rounds; stats[2] = (double)undone; stats[3] = min_area; }
-    free(B_indptr); free(B_indices); free(insum); free(ids); free(done); free(todo); free(et); free(etnm);
+    free(B_indptr); free(B_indices); free(ids); free(done); free(et); free(etnm);
     return 0;
 }
 

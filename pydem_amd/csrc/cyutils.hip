@@ -9,12 +9,25 @@
 // round's pushes, a target that is already done and lies on the tile edge is skipped, a target becomes
 // part of the next frontier when all its CSR upstream cells are done, and the loop ends when the
 // frontier repeats itself (normally: is empty).  Differences: frontiers are lists (the Cython code
-// rescans all N cells four times per round).  The additions into one target within a round keep the
-// Cython order -- ascending source id -- without floating-point atomics: a round first collects its
-// targets, then every target PULLS over its CSR row (scipy's tocsr keeps the column indices sorted)
-// from the sources that are in the round's frontier; results are bit-identical run to run.
+// rescans all N cells four times per round).
+// What is guaranteed: area, done, the taints and the final ids are those of the Cython loops bit for bit,
+// and bit-identical run to run, on every input on which those loops end (they do not end on every
+// input, and then neither does this).  How:
+//  * The Cython loop walks the frontier in ascending id and every push reads the CURRENT value of its
+//    source.  As long as no accepted target of a round is itself in the round's frontier, no push reads a
+//    value written in its round, and only the order of the additions into one target shows: the round
+//    collects its targets, then every target PULLS over its CSR row from the sources that are in the
+//    frontier -- ascending source id, a source's entries in column order -- without floating-point
+//    atomics.  This needs CSR rows of sorted, unique source ids; the Python wrapper brings them to that
+//    form (the reference uses the CSR only as a set).
+//  * A round in which an accepted target IS in the running frontier (cells that drain into each other
+//    and were seeded together, a chain seeded along its length: what the reference's re-seed after a
+//    stall does on level ground) is run in the Cython order on the host: k_cy_targets raises a flag that
+//    rides on the target counter's readback, the state comes down, one plain C++ loop walks the sorted
+//    frontier, and the state goes back up (cy_ordered_round).
 #include "internal.h"
 #include <string.h>
+#include <algorithm>
 
 namespace {
 
@@ -44,16 +57,18 @@ __device__ __forceinline__ int32_t agg_slot(int32_t *count)
     return base + __popcll(bal & ((1ull << lane) - 1ull));
 }
 
-// phase 1 of a round: the distinct targets of the frontier (cyutils.pyx:155-161)
+// phase 1 of a round: the distinct targets of the frontier (cyutils.pyx:155-161), and whether one of them is a member of it
 __global__ void k_cy_targets(const int32_t *__restrict__ front, int32_t nf, const uint8_t *__restrict__ done,
                              const int32_t *__restrict__ col_indptr, const int32_t *__restrict__ col_indices, int64_t n_rows,
-                             int64_t n_cols, int skip_edge, int32_t *tmark, int32_t tag, int32_t *targets, int32_t *n_targets)
+                             int64_t n_cols, int skip_edge, int32_t *tmark, int32_t tag, int32_t *targets, int32_t *n_targets,
+                             const int32_t *__restrict__ mark, int32_t *in_front)
 {
     for (int32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nf; q += gridDim.x * blockDim.x) {
         const int32_t i = front[q];
         for (int32_t j = col_indptr[i]; j < col_indptr[i + 1]; j++) {
             const int32_t row = col_indices[j];
             if ((skip_edge || done[row]) && cy_on_edge(row, n_rows, n_cols)) continue;          // :159-161
+            if (mark[row] == tag - 1) *in_front = 1;      // a target inside the running frontier: the round needs the Cython order
             if (atomicExch(&tmark[row], tag) != tag) targets[agg_slot(n_targets)] = row;
         }
     }
@@ -121,6 +136,36 @@ int front_from_mask(const uint8_t *mask, int64_t n, std::vector<int32_t> &out)
     return 0;
 }
 
+// One round in the Cython order (:151-185) on host copies of the state: the frontier in ascending id, every push reading the
+// current value of its source.  `stamp` (N entries, zero before the call's first ordered round) plays the part of the device
+// marks: tag - 1 for the members of the running frontier, tag for those of the next.
+void cy_ordered_round(std::vector<int32_t> &front, double *area, const uint8_t *done, const int32_t *col_indptr,
+                      const int32_t *col_indices, const double *col_data, const int32_t *row_indptr, const int32_t *row_indices,
+                      int64_t n_rows, int64_t n_cols, double *edge_todo, double *edge_todo_nm, int skip_edge,
+                      std::vector<int32_t> &stamp, int32_t tag, std::vector<int32_t> &next, int32_t *n_repeat)
+{
+    std::sort(front.begin(), front.end());
+    for (int32_t i : front) stamp[(size_t)i] = tag - 1;
+    next.clear();
+    *n_repeat = 0;
+    for (int32_t i : front)
+        for (int32_t j = col_indptr[i]; j < col_indptr[i + 1]; j++) {
+            const int64_t row = col_indices[j];
+            const double w = col_data[j];
+            if ((skip_edge || done[row]) && (row < n_cols || row >= n_cols * n_rows - n_cols || row % n_cols == 0 ||
+                                             row % n_cols == n_cols - 1)) continue;                 // :159-161
+            area[row] += area[i] * w;                                                                // :163
+            if (edge_todo) edge_todo[row] += edge_todo[i] * w;
+            if (edge_todo_nm) edge_todo_nm[row] += edge_todo_nm[i] * w;
+            bool wait = false;
+            for (int32_t k = row_indptr[row]; k < row_indptr[row + 1] && !wait; k++) wait = !done[row_indices[k]];   // :173-179
+            if (wait || stamp[(size_t)row] == tag) continue;
+            if (stamp[(size_t)row] == tag - 1) ++*n_repeat;
+            stamp[(size_t)row] = tag;
+            next.push_back((int32_t)row);
+        }
+}
+
 }  // namespace
 
 extern "C" {
@@ -133,9 +178,10 @@ int pydem_drain_area(double *area, uint8_t *done, uint8_t *ids, const int32_t *c
     const int64_t N = n_rows * n_cols;
     if (N >= INT32_MAX) { pydem_set_error("graph too large for int32 ids"); return -2; }
     const int64_t nnz = col_indptr[N];
+    const int64_t nnz_r = row_indptr[N];      // rows of unique sources: fewer entries than the CSC where it lists an edge twice
     DevTemp d_area, d_done, d_cp, d_ci, d_cd, d_rp, d_ri, d_et, d_etn, d_mark, d_q0, d_q1, d_cnt, d_tmark, d_targets;
     PYDEM_TRY(d_area.alloc(N * 8)); PYDEM_TRY(d_done.alloc(N)); PYDEM_TRY(d_cp.alloc((N + 1) * 4)); PYDEM_TRY(d_ci.alloc(nnz * 4));
-    PYDEM_TRY(d_cd.alloc(nnz * 8)); PYDEM_TRY(d_rp.alloc((N + 1) * 4)); PYDEM_TRY(d_ri.alloc(nnz * 4));
+    PYDEM_TRY(d_cd.alloc(nnz * 8)); PYDEM_TRY(d_rp.alloc((N + 1) * 4)); PYDEM_TRY(d_ri.alloc(nnz_r * 4));
     PYDEM_TRY(d_mark.alloc(N * 4)); PYDEM_TRY(d_q0.alloc(N * 4)); PYDEM_TRY(d_q1.alloc(N * 4)); PYDEM_TRY(d_cnt.alloc(16));
     PYDEM_TRY(d_tmark.alloc(N * 4)); PYDEM_TRY(d_targets.alloc(N * 4));
     if (edge_todo) PYDEM_TRY(d_et.alloc(N * 8));
@@ -146,7 +192,7 @@ int pydem_drain_area(double *area, uint8_t *done, uint8_t *ids, const int32_t *c
     HIP_TRY(hipMemcpy(d_ci.p, col_indices, nnz * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_cd.p, col_data, nnz * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_rp.p, row_indptr, (N + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ri.p, row_indices, nnz * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ri.p, row_indices, nnz_r * 4, hipMemcpyHostToDevice));
     if (edge_todo) HIP_TRY(hipMemcpy(d_et.p, edge_todo, N * 8, hipMemcpyHostToDevice));
     if (edge_todo_no_mask) HIP_TRY(hipMemcpy(d_etn.p, edge_todo_no_mask, N * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(d_mark.p, 0, N * 4));
@@ -159,29 +205,49 @@ int pydem_drain_area(double *area, uint8_t *done, uint8_t *ids, const int32_t *c
     int32_t tag = 2;      // marks: tag of the round in which a cell entered a frontier
     int cur = 0;
     // (the initial frontier carries tag 1 so that "same frontier again" can be recognised in round 1)
+    std::vector<int32_t> stamp, next;      // host side of an ordered round
     for (int64_t r = 0;; r++) {
+        int32_t n_next = 0, n_rep = 0;
         if (nf > 0) {
             const int g = (int)(cdiv(nf, 256) < 2048 ? cdiv(nf, 256) : 2048);
             hipLaunchKernelGGL(k_cy_mark_done, dim3(g), dim3(256), 0, 0, q[cur], nf, d_done.as<uint8_t>(), d_mark.as<int32_t>(), tag);
             HIP_TRY(hipMemset(d_cnt.p, 0, 16));
             hipLaunchKernelGGL(k_cy_targets, dim3(g), dim3(256), 0, 0, q[cur], nf, d_done.as<uint8_t>(), d_cp.as<int32_t>(), d_ci.as<int32_t>(),
-                               n_rows, n_cols, skip_edge, d_tmark.as<int32_t>(), tag, d_targets.as<int32_t>(), d_cnt.as<int32_t>() + 2);
-            int32_t nt = 0;
-            HIP_TRY(hipMemcpy(&nt, d_cnt.as<int32_t>() + 2, 4, hipMemcpyDeviceToHost));
-            if (nt > 0) {
-                const int gt = (int)(cdiv(nt, 256) < 2048 ? cdiv(nt, 256) : 2048);
-                hipLaunchKernelGGL(k_cy_pull, dim3(gt), dim3(256), 0, 0, d_targets.as<int32_t>(), nt, d_area.as<double>(), d_done.as<uint8_t>(),
-                                   d_cp.as<int32_t>(), d_ci.as<int32_t>(), d_cd.as<double>(), d_rp.as<int32_t>(), d_ri.as<int32_t>(),
-                                   edge_todo ? d_et.as<double>() : nullptr, edge_todo_no_mask ? d_etn.as<double>() : nullptr,
-                                   d_mark.as<int32_t>(), tag, q[1 - cur], d_cnt.as<int32_t>(), d_cnt.as<int32_t>() + 1);
+                               n_rows, n_cols, skip_edge, d_tmark.as<int32_t>(), tag, d_targets.as<int32_t>(), d_cnt.as<int32_t>() + 2,
+                               d_mark.as<int32_t>(), d_cnt.as<int32_t>() + 3);
+            int32_t tc[2] = {0, 0};       // targets, and whether one of them is in the running frontier
+            HIP_TRY(hipMemcpy(tc, d_cnt.as<int32_t>() + 2, 8, hipMemcpyDeviceToHost));
+            const int32_t nt = tc[0];
+            if (tc[1]) {
+                // the Cython order, on the host, in the caller's arrays (they take the results at the end anyway)
+                HIP_TRY(hipMemcpy(area, d_area.p, N * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(done, d_done.p, N, hipMemcpyDeviceToHost));
+                if (edge_todo) HIP_TRY(hipMemcpy(edge_todo, d_et.p, N * 8, hipMemcpyDeviceToHost));
+                if (edge_todo_no_mask) HIP_TRY(hipMemcpy(edge_todo_no_mask, d_etn.p, N * 8, hipMemcpyDeviceToHost));
+                front.resize((size_t)nf);
+                HIP_TRY(hipMemcpy(front.data(), q[cur], (size_t)nf * 4, hipMemcpyDeviceToHost));
+                if (stamp.empty()) stamp.assign((size_t)N, 0);
+                cy_ordered_round(front, area, done, col_indptr, col_indices, col_data, row_indptr, row_indices, n_rows, n_cols,
+                                 edge_todo, edge_todo_no_mask, skip_edge, stamp, tag, next, &n_rep);
+                n_next = (int32_t)next.size();
+                HIP_TRY(hipMemcpy(d_area.p, area, N * 8, hipMemcpyHostToDevice));
+                if (edge_todo) HIP_TRY(hipMemcpy(d_et.p, edge_todo, N * 8, hipMemcpyHostToDevice));
+                if (edge_todo_no_mask) HIP_TRY(hipMemcpy(d_etn.p, edge_todo_no_mask, N * 8, hipMemcpyHostToDevice));
+                if (n_next > 0) HIP_TRY(hipMemcpy(q[1 - cur], next.data(), (size_t)n_next * 4, hipMemcpyHostToDevice));
+            } else {
+                if (nt > 0) {
+                    const int gt = (int)(cdiv(nt, 256) < 2048 ? cdiv(nt, 256) : 2048);
+                    hipLaunchKernelGGL(k_cy_pull, dim3(gt), dim3(256), 0, 0, d_targets.as<int32_t>(), nt, d_area.as<double>(), d_done.as<uint8_t>(),
+                                       d_cp.as<int32_t>(), d_ci.as<int32_t>(), d_cd.as<double>(), d_rp.as<int32_t>(), d_ri.as<int32_t>(),
+                                       edge_todo ? d_et.as<double>() : nullptr, edge_todo_no_mask ? d_etn.as<double>() : nullptr,
+                                       d_mark.as<int32_t>(), tag, q[1 - cur], d_cnt.as<int32_t>(), d_cnt.as<int32_t>() + 1);
+                }
+                HIP_TRY(hipGetLastError());
+                int32_t h[2];
+                HIP_TRY(hipMemcpy(h, d_cnt.p, 8, hipMemcpyDeviceToHost));
+                n_next = h[0]; n_rep = h[1];
             }
-            HIP_TRY(hipGetLastError());
-        } else {
-            HIP_TRY(hipMemset(d_cnt.p, 0, 16));
         }
-        int32_t h[2];
-        HIP_TRY(hipMemcpy(h, d_cnt.p, 8, hipMemcpyDeviceToHost));
-        const int32_t n_next = h[0], n_rep = h[1];
         // keep_going = (ids != ids_old)  (:187): stop when the new frontier equals the old one
         const bool same = (n_next == nf) && (n_rep == n_next);
         cur = 1 - cur; nf = n_next; tag++;

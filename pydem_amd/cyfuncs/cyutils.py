@@ -36,6 +36,24 @@ def _f64_inplace(a, name, size):
     return a
 
 
+def _sorted_unique_rows(rp, ri, N):
+    """The CSR index structure with every row's source ids ascending and listed once: the form in which the library's pull adds
+    in the Cython order.  The reference reads the CSR only as a set, so rows in any order, or with a source listed twice (tocsr()
+    of a CSC with unsummed duplicates), mean the same graph.  A row-wise check first: scipy's tocsr() of a canonical CSC passes."""
+    nr = int(rp[-1])
+    if nr < 2:
+        return rp, ri
+    rising = ri[1:nr] > ri[:nr - 1]
+    starts = rp[1:-1]
+    rising[starts[(starts > 0) & (starts < nr)] - 1] = True          # a row's first entry answers to nothing before it
+    if rising.all():
+        return rp, ri
+    key = np.unique(np.repeat(np.arange(N, dtype=np.int64), np.diff(rp)) * N + ri[:nr])
+    rp2 = np.zeros(N + 1, np.int32)
+    rp2[1:] = np.cumsum(np.bincount(key // N, minlength=N))
+    return rp2, (key % N).astype(np.int32)
+
+
 def drain_connections(arr, ids, indptr, indices, set_to=0, device=0):
     """cyutils.drain_connections (cyutils.pyx:35-46): flood `set_to` from the cells in `ids` along the
     CSC columns; updates and returns `arr`."""
@@ -66,16 +84,18 @@ def drain_area(area, done, ids, col_indptr, col_indices, col_data, row_indptr, r
     cp = _i32(col_indptr, 'col_indptr', size=N + 1)
     rp = _i32(row_indptr, 'row_indptr', size=N + 1)
     nnz = int(cp[-1])
-    if nnz < 0 or int(rp[-1]) != nnz:
-        raise ValueError("col_indptr and row_indptr describe different numbers of edges")
+    nnz_r = int(rp[-1])           # not nnz where one of the two lists an edge twice: the CSR stands for a set of sources
+    if nnz < 0 or nnz_r < 0 or (nnz == 0) != (nnz_r == 0) or np.any(np.diff(cp) < 0) or np.any(np.diff(rp) < 0):
+        raise ValueError("col_indptr / row_indptr do not describe a graph")
     ci = _i32(col_indices, 'col_indices', at_least=nnz)
-    ri = _i32(row_indices, 'row_indices', at_least=nnz)
+    ri = _i32(row_indices, 'row_indices', at_least=nnz_r)
     data = np.ascontiguousarray(col_data, np.float64)
     if data.ndim != 1 or data.size < nnz:
         raise ValueError("col_data has %d entries, expected >= %d" % (data.size, nnz))
-    for nm, ix in (('col_indices', ci), ('row_indices', ri)):
-        if nnz and (ix[:nnz].min() < 0 or ix[:nnz].max() >= N):
+    for nm, ix, nz in (('col_indices', ci, nnz), ('row_indices', ri, nnz_r)):
+        if nz and (ix[:nz].min() < 0 or ix[:nz].max() >= N):
             raise ValueError("%s out of range" % nm)
+    rp, ri = _sorted_unique_rows(rp, ri, N)
     if nnz == 0:
         ci = np.zeros(1, np.int32); ri = np.zeros(1, np.int32); data = np.zeros(1)
     if edge_todo is not None:
@@ -88,4 +108,5 @@ def drain_area(area, done, ids, col_indptr, col_indices, col_data, row_indptr, r
                                            cp.ctypes.data_as(_P), ci.ctypes.data_as(_P), data.ctypes.data_as(_P),
                                            rp.ctypes.data_as(_P), ri.ctypes.data_as(_P), int(n_rows), int(n_cols),
                                            et, etn, int(skip_edge), device))
-    return area, done, edge_todo, edge_todo_no_mask
+    # (a taint array that was left out comes back as the stand-in of one zero that the Cython function puts in its place)
+    return area, done, np.zeros(1) if edge_todo is None else edge_todo, np.zeros(1) if edge_todo_no_mask is None else edge_todo_no_mask
