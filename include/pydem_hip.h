@@ -34,7 +34,9 @@
  *                             inventory of the mosaic (_label, _label_roots, _get_id_lines, _inventory, _labels) -- no reference method
  *   pydem_depressions         the depression inventory of the resident elevation (the classic fill in scratch, a block union-find
  *                             over the raised cells, integer per-label reductions) -- no reference method
- *   pydem_twi                 DEMProcessor.calc_twi                pydem/dem_processing.py:1647-1677
+ *   pydem_hand_table          per zone and water stage, the cells, flooded area, area x HAND and wetted bed area of a HAND plane (one
+ *                             pass, fixed-point sums under integer atomics) -- no reference method
+ *   pydem_twi                 DEMProcessor.calc_twi               pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
  * the opaque pydem_tile handle (create / upload / run / download / destroy).  Nothing allocated
@@ -331,6 +333,41 @@ int pydem_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
                       int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms);
 /* The table of the last pydem_depressions on this tile: `rows` must be its *n_kept (-2 otherwise). */
 int pydem_depressions_table(pydem_tile *t, int64_t rows, pydem_depression *table);
+/* The HAND hydraulic table: per zone (a reach's catchment) and per water stage, the cells, the flooded area, the area-weighted
+ * HAND and the wetted bed area of a HAND plane -- what a synthetic rating curve is made of; no reference method.
+ * INPUTS.  The tile's spacing and the resident PYDEM_MAG (-3 without either).  zone: host int32 [n,m]; 1..K are zones, anything
+ * < 1 is skipped, a value > K is an error (-2).  hand: host float64 [n,m], or NULL: the result plane of the last pydem_dist_down
+ * as it stands on the device (RESIDENT HAND below).  stages: host float64 [S], finite, strictly ascending, 1 <= S <= 1024 (-2
+ * otherwise).  K = n_zones >= 0.
+ * DEFINITION.  Row r has the cell area a = dX2[r] * dY2[r], one multiply.  A cell c of zone k with h = hand[c]:
+ *   h is NaN                      adds 1 to nan[k];
+ *   h > stages[S-1] (+inf too)    adds 1 to above[k];
+ *   otherwise it is COUNTED in bin b = the number of stages < h (np.searchsorted(stages, h, 'left'): h == stages[j] lies in bin j,
+ *                                 -0.0 == 0.0; a negative h is allowed and lies in bin 0 when h <= stages[0]).
+ * A counted cell adds to the four int64 words of (k, b):  1;  llrint(ldexp(p, shift)) for p_a = a;  the same for p_m = fl(a * h)
+ * (signed);  the same for p_b = fl(a * sqrt(fl(1 + fl(mag*mag)))) with the correctly rounded square root and mag = PYDEM_MAG[c]
+ * (a non-finite mag counts as slope 0: p_b = a).  The three shifts are those of pydem_depressions: with E from frexp of the
+ * largest term -- max p_a, max |p_m|, max p_b over the counted cells, 0 when there are none -- and B = min(40, 62 -
+ * ceil(log2(max(n*m, 2)))) fraction bits, shift = B - E and the quantum is q = 2^(E - B).  A first kernel finds the three maxima
+ * with integer atomicMax on the bit patterns of the magnitudes; the host forms the shifts.  Integers only from there on: every
+ * schedule gives the same bits, the host twin (pydem_amd/hydraulics.py: hand_table_ref) is compared with array_equal, and per
+ * word |word * q - sum of p| <= cells * q / 2.  A term that is not finite (h = -inf, an overflowing slope) is refused: -2.
+ * OUTPUTS (host).  table: int64 [K, S, 4]: cells, area, area x HAND, bed area of (zone, bin) -- per bin, NOT cumulated over the
+ * stages.  skipped: int64 [K, 2]: nan, above.  quanta[3]: q_a, q_m, q_b.  ms[3] (may be NULL): device time (hipEvent pairs) of
+ * the two kernels together, of the maxima, of the sums (the table's memset included).
+ * MEMORY.  The table and the uploaded planes are leased from the conditioning arena; nothing stays with the tile, and
+ * pydem_tile_device_bytes is what it was before.  -6 with a message, before any kernel runs, when the device cannot hold the
+ * K * S * 4 + K * 2 words of the table.
+ * RESIDENT HAND (hand == NULL).  The tile carries a tag that says its result plane holds a finished pydem_dist_down: set at the
+ * successful end of pydem_dist_down alone; cleared when any sweep that shares that plane (pydem_dist_down / _dist_up / _rev_accum /
+ * _fwd_accum / _stream_network / _tree_accum) takes it, and wherever the flow graph is invalidated (an upload of elevation, slope,
+ * direction or flats, a conditioning stage, pydem_slopes_directions ...).  -3 when the tag is not set.  The plane is only read.
+ * Both ways give the same bytes.
+ * PYDEM_HANDTAB_LOCAL=0 (read once per process): no reduction across the wavefront, every lane issues its own atomics -- the
+ * same result by another schedule, for the tests.  Writes no field, flag or timing of the tile. */
+int pydem_hand_table(pydem_tile *t, const int32_t *zone /* [n,m] host */, const double *hand /* [n,m] host, or NULL */,
+                     const double *stages /* [n_stages] host */, int64_t n_stages, int64_t n_zones, int64_t *table /* [K,S,4] host */,
+                     int64_t *skipped /* [K,2] host */, double *quanta /* [3] */, double *ms /* [3] */);
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
 /* What the tile knows about its flats mask against its slopes, and what the pydem_find_flats calls on it have launched so far

@@ -88,6 +88,7 @@ SYMBOLS = {
     'pydem_depressions': (C.c_int, [_P, _P, C.c_double, C.c_int64, C.c_double, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P,
                                     C.POINTER(C.c_int64), _P]),
     'pydem_depressions_table': (C.c_int, [_P, C.c_int64, _P]),
+    'pydem_hand_table': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     'pydem_pit_candidates': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'pydem_pit_candidates_read': (C.c_int, [_P, C.c_int64, _P, _P]),
     'pydem_pit_paths': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
@@ -446,6 +447,26 @@ class Tile(object):
         check(self.lib.pydem_depressions_table(self._h, int(kept.value), rows.ctypes.data_as(_P)))
         return label, rows, dict(n_found=int(found.value), quanta=(float(quanta[0]), float(quanta[1])), passes=int(passes.value),
                                  ms=dict(zip(self.DEPRESSION_PARTS, ms.tolist())))
+
+    HAND_TABLE_PARTS = ('total', 'maxima', 'sums')
+
+    def hand_table(self, zone, stages, K, hand=None):
+        """pydem_hand_table: (int64 [K, S, 4] -- cells, area, area x HAND, bed area per zone and bin --, int64 [K, 2] -- NaN cells,
+        cells above the top stage --, quanta (area, area x HAND, bed area), {part: device ms}).  zone: int32 ids of the tile's
+        shape, 1..K; hand: float64 of the tile's shape, or None: the result plane of the last dist_down as it stands on the
+        device.  The library checks the stages and the ids (HipError -2)."""
+        zone = np.ascontiguousarray(zone, np.int32)
+        if zone.shape != self.shape:
+            raise ValueError("zone plane of shape %r for a tile of shape %r" % (zone.shape, self.shape))
+        h = None if hand is None else self._plane(hand, 'HAND plane')
+        st = np.ascontiguousarray(stages, np.float64).ravel()
+        K = int(K)
+        ints = np.zeros((max(K, 0), st.size, 4), np.int64)
+        skipped = np.zeros((max(K, 0), 2), np.int64)
+        quanta, ms = np.zeros(3), np.zeros(len(self.HAND_TABLE_PARTS))
+        check(self.lib.pydem_hand_table(self._h, _ptr(zone), _ptr(h), _ptr(st), st.size, K, _ptr(ints), _ptr(skipped), _ptr(quanta),
+                                        _ptr(ms)))
+        return ints, skipped, tuple(float(v) for v in quanta), dict(zip(self.HAND_TABLE_PARTS, ms.tolist()))
 
     def pit_drain_paths(self, below_sea, max_iter, max_dist, max_dist_XY, sort_dtype=None):
         """calc_pit_drain_paths on the resident elevation.  Returns (n_failed, iterations used, rounds), or None when the tile

@@ -558,6 +558,7 @@ static int dist_upload(pydem_tile *t, T **plane, const T *src)
 static int dist_state(pydem_tile *t, DistArgs &A, int kind, int stat)
 {
     const int64_t ntiles = cdiv(t->m, DD_T) * cdiv(t->n, DD_T);
+    t->dd_down_ready = false;           // whoever takes the state writes the result plane: pydem_dist_down sets it again at its end
     PYDEM_TRY(tile_alloc(t, &t->dd_out, (size_t)t->NN));
     PYDEM_TRY(tile_alloc(t, &t->dd_queue, (size_t)t->NN));
     PYDEM_TRY(tile_alloc(t, &t->dd_ctr, (size_t)(DD_WORDS + 4 * ntiles)));

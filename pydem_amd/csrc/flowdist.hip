@@ -166,8 +166,10 @@ extern "C" int pydem_dist_down(pydem_tile *t, int kind, int stat, const uint8_t 
     DistArgs A;
     PYDEM_TRY(dist_state(t, A, kind, stat));
     const DownClassify targets = {target ? (const double *)nullptr : (const double *)t->uca, uca_threshold};
-    return dist_sweep<dd_release>(t, "dist_down", DD_MIN_PER_VISIT, A, targets, DownFinish{}, k_dd_recount,
+    PYDEM_TRY(dist_sweep<dd_release>(t, "dist_down", DD_MIN_PER_VISIT, A, targets, DownFinish{}, k_dd_recount,
         [&](dim3 grid, int32_t pass, int tiles_x, int tiles_y, int32_t *tile_state) {
             hipLaunchKernelGGL(k_dd_tiles, grid, dim3(256), 0, t->stream, A, pass, tiles_x, tiles_y, tile_state);
-        }, out, ms, levels, n_unresolved);
+        }, out, ms, levels, n_unresolved));
+    t->dd_down_ready = true;            // the result plane is a finished downslope distance (pydem_hand_table reads it in place)
+    return 0;
 }

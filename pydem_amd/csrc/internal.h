@@ -139,6 +139,10 @@ struct pydem_tile {
     uint8_t *ta_sc = nullptr;
     int32_t *dd_ctr = nullptr, *dd_h_ctr = nullptr;
     hipEvent_t dd_ev[2] = {nullptr, nullptr};
+    // dd_out holds the finished result of a pydem_dist_down on the resident graph and surface: set at the successful end of
+    // pydem_dist_down alone, cleared where a sweep takes the shared state (dist_state) and where the flow graph is dropped
+    // (tile_graph_drop).  pydem_hand_table reads the plane in place under it
+    bool dd_down_ready = false;
     void *scratch = nullptr; size_t scratch_bytes = 0;
     // pydem_fill_seam_* (fill_depressions.hip), one session at a time: W of the open session (a plane), the flag words of its
     // 32 x 32 blocks and its cap lines (top m, bottom m, left n, right n doubles; +inf: no cap), all three held from begin to end;
@@ -246,6 +250,8 @@ int stage_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t n_rows,
 int stage_fill_seam_labels(pydem_tile *t, const int32_t *lut, int32_t *label, double *ms);
 int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, int64_t min_cells, double min_volume, int32_t *label,
                       int64_t *n_found, int64_t *n_kept, double *quanta, int64_t *passes, double *ms);
+int stage_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, const double *stages, int64_t n_stages, int64_t n_zones,
+                     int64_t *table, int64_t *skipped, double *quanta, double *ms);
 int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);
 int stage_pit_candidates_read(pydem_tile *t, int64_t npits, int32_t *cells, double *elev);
 int stage_pit_paths(pydem_tile *t, const int32_t *order_host, int64_t npits, int max_iter, int max_dist, double max_dist_XY,
@@ -255,6 +261,9 @@ int stage_synth(pydem_tile *t, uint32_t seed, int64_t row0, int64_t col0, int n_
 int bench_stencil(pydem_tile *t, int iters, double *avg_ms);
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the flow graph no longer matches the resident elev / mag / dir / flats; what was swept on it is stale with it
+static inline void tile_graph_drop(pydem_tile *t) { t->graph_valid = false; t->dd_down_ready = false; }
 
 // PYDEM_STEP_LEAN=0 (read per call: the tests switch it): the step as it was before the redundant mask passes, copies and host
 // waits between the big stages were taken out

@@ -312,7 +312,7 @@ int pydem_tile_upload(pydem_tile *t, int field, const void *src, int dtype)
     t->have[field] = true;
     if (field == PYDEM_MAG || field == PYDEM_FLATS) t->flats_state = 0;
     if (field == PYDEM_ELEV) { t->elev_f32 = (dtype == PYDEM_F32); t->elev_dtype = dtype; }
-    if (field == PYDEM_ELEV || field == PYDEM_MAG || field == PYDEM_DIRECTION || field == PYDEM_FLATS) t->graph_valid = false;
+    if (field == PYDEM_ELEV || field == PYDEM_MAG || field == PYDEM_DIRECTION || field == PYDEM_FLATS) tile_graph_drop(t);
     return 0;
 }
 
@@ -374,7 +374,7 @@ static int line_copy(pydem_tile *t, int field, int axis, int64_t index, void *ho
     }
     HIP_TRY(hipStreamSynchronize(t->stream));
     if (to_host) memcpy(user, pin, nbytes);
-    if (!to_host && (field == PYDEM_ELEV || field == PYDEM_MAG || field == PYDEM_DIRECTION || field == PYDEM_FLATS)) t->graph_valid = false;
+    if (!to_host && (field == PYDEM_ELEV || field == PYDEM_MAG || field == PYDEM_DIRECTION || field == PYDEM_FLATS)) tile_graph_drop(t);
     if (!to_host && (field == PYDEM_MAG || field == PYDEM_FLATS)) t->flats_state = 0;
     return 0;
 }
@@ -438,7 +438,7 @@ int pydem_tile_synth_fractal(pydem_tile *t, uint32_t seed, int64_t row0, int64_t
                              int top_shift, double zmin, double zrange)
 {
     HIP_TRY(hipSetDevice(t->device));
-    t->graph_valid = false;
+    tile_graph_drop(t);
     t->flats_state = 0;
     PYDEM_TRY(ensure_field(t, PYDEM_ELEV));
     PYDEM_TRY(stage_synth(t, seed, row0, col0, n_octaves, top_shift, zmin, zrange));
@@ -464,7 +464,7 @@ int pydem_slopes_directions(pydem_tile *t)
     if (!t->spacing_set) { pydem_set_error("pydem_slopes_directions: call pydem_tile_set_spacing first"); return -3; }
     PYDEM_TRY(ensure_fields(t, {PYDEM_MAG, PYDEM_DIRECTION, PYDEM_FLATS}));
     PYDEM_TRY(tile_alloc(t, &t->flat0, (size_t)t->NN));
-    t->graph_valid = false;
+    tile_graph_drop(t);
     t->flats_state = 0;
     PYDEM_TRY(stage_stencil(t));
     PYDEM_TRY(stage_flats(t));          // (leaves flats_state 1 when flats == (mag == -1) is known to hold)
@@ -479,7 +479,7 @@ int pydem_fill_flats(pydem_tile *t, double max_pit_area, int below_sea, double s
     t->einc_ready = false;
     HIP_TRY(hipSetDevice(t->device));
     PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_fill_flats"));
-    t->graph_valid = false;
+    tile_graph_drop(t);
     t->flats_state = 0;                 // (mag and the other planes are work planes of the conditioning)
     const int r = stage_fill_flats(t, max_pit_area, below_sea, source_tol, peaks, pits, artefacts_only);
     if (r < 0) return r;
@@ -499,7 +499,7 @@ int pydem_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     PYDEM_TRY(stage_fill_depressions(t, epsilon, outlets, depth, n_raised, max_depth, passes, ms));
     t->edge_clean = false;
     t->einc_ready = false;
-    t->graph_valid = false;
+    tile_graph_drop(t);
     t->flats_state = 0;
     for (int f = PYDEM_MAG; f < PYDEM_FIELD_COUNT; f++) t->have[f] = false;     // as after the other conditioning stages
     return 0;
@@ -538,7 +538,7 @@ int pydem_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_rai
     if (rc == -2 || rc == -5) return rc;            // refused: the surface is what it was
     t->edge_clean = false;
     t->einc_ready = false;
-    t->graph_valid = false;
+    tile_graph_drop(t);
     t->flats_state = 0;
     for (int f = PYDEM_MAG; f < PYDEM_FIELD_COUNT; f++) t->have[f] = false;     // as after pydem_fill_depressions
     return rc;
@@ -596,6 +596,15 @@ int pydem_depressions_table(pydem_tile *t, int64_t rows, pydem_depression *table
     return 0;
 }
 
+int pydem_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, const double *stages, int64_t n_stages, int64_t n_zones,
+                     int64_t *table, int64_t *skipped, double *quanta, double *ms)
+{
+    if (!t) { pydem_set_error("pydem_hand_table: no tile"); return -2; }
+    HIP_TRY(hipSetDevice(t->device));
+    // reads the slope, the spacing and (without a HAND plane) the result plane of pydem_dist_down: no field, flag or timing changes
+    return stage_hand_table(t, zone, hand, stages, n_stages, n_zones, table, skipped, quanta, ms);
+}
+
 int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
 {
     HIP_TRY(hipSetDevice(t->device));
@@ -619,7 +628,7 @@ int pydem_pit_paths(pydem_tile *t, const int32_t *order, int64_t npits, int max_
     PYDEM_TRY(need(t, PYDEM_ELEV, "pydem_pit_paths"));
     // the path values get the dtype of the array the reference edits (:539): integer surfaces truncate them, float32 ones round
     const int dtype_mode = t->elev_dtype == PYDEM_F64 ? 0 : (t->elev_dtype == PYDEM_F32 ? 2 : 1);
-    t->graph_valid = false;
+    tile_graph_drop(t);
     t->flats_state = 0;
     const int r = stage_pit_paths(t, order, npits, max_iter, max_dist, max_dist_XY, n_failed, iter_used, rounds, dtype_mode);
     if (r < 0) return r;
@@ -769,7 +778,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
         if (off) PYDEM_TRY(planes.alloc(off));
         for (const Kept &k : kept)
             HIP_TRY(hipMemcpyAsync((char *)planes.p + k.off, k.dst, k.bytes, hipMemcpyDeviceToDevice, t->stream));
-        t->graph_valid = false;
+        tile_graph_drop(t);
     }
     int rc = own_graph ? ensure_graph(t, opt, "pydem_uca_weighted") : 0;
     if (rc == 0) {
@@ -794,7 +803,7 @@ int pydem_uca_weighted(pydem_tile *t, pydem_options *opt, int scale_by_cell_area
             HIP_TRY(hipMemcpyAsync(k.dst, (char *)planes.p + k.off, k.bytes, hipMemcpyDeviceToDevice, t->stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(t->stream));
-        t->graph_valid = false;
+        tile_graph_drop(t);
     }
     if (own_graph) t->flats_state = 0;      // (the graph stage patched mag / flats and they were written back: nothing is claimed about them)
     if (rc != 0) return rc;

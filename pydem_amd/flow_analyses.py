@@ -436,3 +436,81 @@ class FlowAnalyses(object):
         self.reach_attributes_stats = dict(ms=sum(st['ms'] for st in stats.values()), sweeps=stats, edge_nan=bool(edge_nan),
                                            n_links=int(table.size))
         return table
+
+    # ------------------------------------------------------------------ HAND hydraulics
+    hand_hydraulics = None        # last calc_hand_hydraulics: a hydraulics.HandHydraulics (no counterpart in the reference)
+    hand_hydraulics_stats = None  # {'ms': {part: device ms}, 'n_links', 'n_stages', 'n_unresolved'} of that call
+    inundation = None             # last calc_inundation
+
+    def calc_hand_hydraulics(self, stages, uca_threshold=None, streams=None, manning_n=0.05, edge_nan=True):
+        """The HAND hydraulic property table and the synthetic rating curve of every reach (the step that follows HAND in the CFIM
+        / NWM HAND workflows; no reference method).  `stages`: 1 .. 1024 water stages above the drainage, finite and strictly
+        ascending.  The streams: `uca_threshold` or `streams` (a boolean mask), exactly one, as for calc_stream_network.  Runs
+        calc_reach_attributes for each reach's length and slope, calc_stream_network for the catchment (basin) of each reach, the
+        HAND sweep of calc_hand, left on the device, and one reduction of that plane over (basin, stage) (pydem_hand_table,
+        include/pydem_hip.h: fixed-point sums, one result whatever the schedule).  Returns a hydraulics.HandHydraulics with one
+        row per link of `stream_network`: per stage the flooded cells, area, volume and wetted bed area of the link's catchment,
+        the reach-averaged top width, cross-section, wetted perimeter and hydraulic radius, and the discharge by Manning's
+        equation with `manning_n` (NaN for a link without a positive slope or length); cells_nan / cells_above count the
+        catchment's cells whose HAND is NaN / above the top stage.  Per tile: a catchment cut by the tile's border is what the
+        tile holds of it (`reach_attributes['complete']` tells).  Kept as `hand_hydraulics`; `hand_hydraulics_stats` holds the
+        device milliseconds per part."""
+        from . import hydraulics
+        st = hydraulics.check_stages(stages)
+        try:
+            n_man = float(manning_n)
+        except (TypeError, ValueError):
+            raise ValueError("manning_n must be a number > 0 (got %r)" % (manning_n,))
+        if not (n_man > 0 and np.isfinite(n_man)):
+            raise ValueError("manning_n must be finite and > 0 (got %r)" % (manning_n,))
+        mask, thr = self._stream_set(streams, uca_threshold)
+        reaches = self.calc_reach_attributes(uca_threshold=thr, streams=mask, edge_nan=edge_nan)
+        net = self.calc_stream_network(uca_threshold=thr, streams=mask, basins=True)
+        K = int(net.links.size)
+        tile = self._on_flow_graph("HAND hydraulic table calculation")
+        _, dd_ms, _, left = tile.dist_down('v', 'ave', mask, thr, download=False)
+        ints, skipped, quanta, ms = tile.hand_table(net.basin, st, K, hand=None)
+        table = hydraulics.hydraulic_table(ints, quanta, st, reaches['length'], reaches['slope'], n_man)
+        res = hydraulics.HandHydraulics(st, net.links['id'], table, skipped[:, 0], skipped[:, 1], reaches['length'], reaches['slope'],
+                                        ints=ints, skipped=skipped, quanta=quanta, zone=net.basin, manning_n=n_man)
+        res.stream_set = (mask, thr)
+        self.hand_hydraulics = res
+        self.hand_hydraulics_stats = dict(
+            ms=dict(reach_attributes=self.reach_attributes_stats['ms'], stream_network=float(sum(self.stream_network_stats['ms'])),
+                    dist_down=dd_ms, hand_table=ms['total'], hand_table_maxima=ms['maxima'], hand_table_sums=ms['sums']),
+            n_links=K, n_stages=int(st.size), n_unresolved=left)
+        if left:
+            warnings.warn("%d cells lie on or upstream of a circular drainage pattern: their HAND is NaN" % left)
+        return res
+
+    def calc_inundation(self, stage=None, discharge=None):
+        """The inundation depth map of `hand_hydraulics` (calc_hand_hydraulics first) for a water `stage` above the drainage or a
+        `discharge` -- exactly one, a scalar for every link or one value per link.  A discharge becomes the stage of each link by
+        linear interpolation over the finite points of its rating curve: below the first point the first stage, above the last
+        NaN (no extrapolation), NaN with a warning where the rating is not non-decreasing.  The depth of a cell is
+        max(stage of its basin's link - HAND, 0); NaN where HAND is NaN and where the cell belongs to no basin.  Host numpy on
+        the HAND plane of calc_hand and the basin plane.  Returns the float64 array, kept as `inundation`."""
+        from . import hydraulics
+        if (stage is None) == (discharge is None):
+            raise ValueError("give exactly one of stage and discharge")
+        hh = self.hand_hydraulics
+        if hh is None:
+            raise ValueError("calc_inundation needs the table of calc_hand_hydraulics: call it first")
+        K = int(hh.link_ids.size)
+        what = 'stage' if stage is not None else 'discharge'
+        try:
+            v = np.asarray(stage if stage is not None else discharge, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number or an array of numbers" % what)
+        if v.ndim == 0:
+            v = np.full(K, float(v))
+        if v.shape != (K,):
+            raise ValueError("%s of shape %r for %d links (a scalar, or one value per link)" % (what, v.shape, K))
+        level = v if stage is not None else hydraulics.stage_for_discharge(hh.stages, hh.discharge, v)
+        if hh.zone is None:
+            raise ValueError("calc_inundation: hand_hydraulics holds no basin plane (a table made by hand)")
+        if hh.hand is None:
+            mask, thr = hh.stream_set
+            hh.hand = self.calc_hand(uca_threshold=thr, target=mask)
+        self.inundation = hydraulics.inundation_depth(hh.hand, hh.zone, level)
+        return self.inundation
