@@ -36,6 +36,8 @@
  *                             over the raised cells, integer per-label reductions) -- no reference method
  *   pydem_hand_table          per zone and water stage, the cells, flooded area, area x HAND and wetted bed area of a HAND plane (one
  *                             pass, fixed-point sums under integer atomics) -- no reference method
+ *   pydem_terrain_attributes  gradient, aspect, profile / plan / tangential / mean curvature and hillshade of the resident elevation from
+ *                             a least-squares quadratic over a (2k+1)^2 window (Evans 1980, Wood 1996) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi               pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -368,6 +370,60 @@ int pydem_depressions_table(pydem_tile *t, int64_t rows, pydem_depression *table
 int pydem_hand_table(pydem_tile *t, const int32_t *zone /* [n,m] host */, const double *hand /* [n,m] host, or NULL */,
                      const double *stages /* [n_stages] host */, int64_t n_stages, int64_t n_zones, int64_t *table /* [K,S,4] host */,
                      int64_t *skipped /* [K,2] host */, double *quanta /* [3] */, double *ms /* [3] */);
+/* Terrain attributes of the resident float64 elevation at a chosen scale: the least-squares quadratic over the (2k+1)^2 window of
+ * every cell (Evans 1980 at k = 1, Wood 1996 above) and what follows from its five derivatives; no reference method.  PYDEM_MAG /
+ * PYDEM_DIRECTION are the steepest of eight triangular facets, not the gradient of the surface; these planes are, and the second
+ * derivatives exist nowhere else.  Apart from one atan2 every plane is a fixed sequence of + - * / sqrt, every one of them correctly
+ * rounded and none contracted, so the host twin (pydem_amd/terrain.py: terrain_attributes_ref) gives the same bits.
+ * DEFINITION, for the cell (r, c) and the half width k.  N = 2k + 1.  Z(j, i) = elev[r + j, c + i] for row offsets j and column
+ * offsets i in -k .. k.  gx = dX2[r], gy = dY2[r]: the centre row's cell size, taken as constant over the window (an approximation
+ * on geographic tiles).  x points east (increasing column), y north (decreasing row).
+ *   Row moments, for each j, each sum started at 0.0 and added in ascending i:
+ *     R0_j = sum Z(j, i);   R1_j = sum (double)i * Z(j, i);   R2_j = sum (double)(i*i) * Z(j, i).
+ *   Window moments, each sum started at 0.0 and added in ascending j:
+ *     M00 = sum R0_j;  M10 = sum R1_j;  M20 = sum R2_j;  M01 = sum (double)j * R0_j;  M02 = sum (double)(j*j) * R0_j;  M11 = sum (double)j * R1_j.
+ *   (A running sum over a sliding window gives other bits and is not the contract.)
+ *   Constants, exact integers held as doubles:  S2 = k(k+1)(2k+1)/3;  S4 = k(k+1)(2k+1)(3k^2+3k-1)/15;  D1 = N * S2;
+ *     D2 = N * S4 - S2 * S2;  D11 = S2 * S2.
+ *   The fit in index units:  d = M10 / D1;  e = M01 / D1;  cxy = M11 / D11;  h = (S2 * M00) / N;  a = (M20 - h) / D2;  b = (M02 - h) / D2.
+ *   Ground units:  p = d / gx;  q = -(e / gy);  r = (2 * a) / (gx * gx);  t = (2 * b) / (gy * gy);  s = -(cxy / (gx * gy)).
+ *   g2 = p*p + q*q;  w = 1.0 + g2;  pq2 = 2 * (p*q);  A = ((p*p)*r + pq2*s) + (q*q)*t;  B = ((q*q)*r - pq2*s) + (p*p)*t.
+ * PLANES (enum pydem_terrain_attr).  Signs follow Florinsky / Shary: positive is convex (ridges, noses, shoulders), negative concave.
+ *   DZDX, DZDY    p, q
+ *   GRADIENT      sqrt(g2): rise over run, the unit of PYDEM_MAG
+ *   ASPECT        the azimuth of the downslope direction, clockwise from north, radians: atan2(-p, -q), plus 2 pi (the double
+ *                 6.283185307179586) when negative; -1 where g2 == 0, as PYDEM_DIRECTION on flats
+ *   PROFILE       -A / (g2 * (w * sqrt(w)));  0 where g2 == 0
+ *   PLAN          -B / (g2 * sqrt(g2)), the contour curvature;  0 where g2 == 0
+ *   TANGENTIAL    -B / (g2 * sqrt(w));  0 where g2 == 0
+ *   MEAN          -(((1 + q*q)*r - pq2*s) + (1 + p*p)*t) / (2 * (w * sqrt(w)))
+ *   HILLSHADE     with zp = z_factor * p, zq = z_factor * q and the unit vector to the sun light = (Le, Ln, Lu) (east, north, up):
+ *                 v = ((Lu - zp*Le) - zq*Ln) / sqrt(1 + (zp*zp + zq*zq));  v where v > 0, else 0
+ * UNDEFINED CELLS.  A cell is defined when its window lies inside the tile and M00 is not NaN, i.e. the window holds no NaN
+ * elevation (+-inf is not no data: it goes through the arithmetic).  Every requested plane is NaN (0x7ff8000000000000) at a cell
+ * that is not defined; a tile smaller than the window is all NaN, which is no error.  *n_defined: the defined cells -- on finite
+ * elevations the cells that are not NaN -- counted with an integer reduction across the wavefront and integer atomics.
+ * ARGUMENTS.  half_width = k, 1 .. 7.  outs: PYDEM_TA_COUNT host planes [n,m] of float64, NULL = not wanted: only the planes
+ * asked for are computed, stored and downloaded.  light: three doubles, may be NULL unless outs[PYDEM_TA_HILLSHADE] is set;
+ * z_factor: finite, > 0.  *ms: device time of the kernel (a hipEvent pair).  -2 (before any launch) for half_width outside 1 .. 7,
+ * no plane asked for, a hillshade without light and a z_factor that is not finite or not > 0; -3 without a spacing or an elevation.
+ * KERNELS (csrc/terrain.hip).  k = 1 marches rows in registers, one lane per column, as the D-infinity stencil does.  k >= 2
+ * stages a block of 30 rows x (64 + 2k) columns with its halo in LDS, forms R0 / R1 / R2 once per staged row and combines them
+ * vertically, one lane per cell.  The cap k <= 7 (a window of 15) is that path's LDS budget: 30 rows x ((64 + 2k) + 3 x 64)
+ * doubles = 64 800 bytes at k = 7, so that two workgroups share the 160 KiB of a CU and 16 of the 30 staged rows are output
+ * rows.  Both paths keep the operand order above and give the same bits at k = 1; PYDEM_TA_GENERIC=1 (read per call) sends k = 1
+ * through the general path, for the tests.
+ * MEMORY.  The planes of a call and its counter are one device block of the tile (8192 bytes + 8 n m bytes per requested plane), grown
+ * to the largest request so far, counted by pydem_tile_device_bytes and freed with the tile.  Reads the elevation and dX2 / dY2;
+ * needs no slope, flats or flow graph.  Writes no field of the tile, no timing and no state of any other analysis. */
+enum pydem_terrain_attr {
+    PYDEM_TA_DZDX = 0, PYDEM_TA_DZDY = 1, PYDEM_TA_GRADIENT = 2, PYDEM_TA_ASPECT = 3, PYDEM_TA_PROFILE = 4, PYDEM_TA_PLAN = 5,
+    PYDEM_TA_TANGENTIAL = 6, PYDEM_TA_MEAN = 7, PYDEM_TA_HILLSHADE = 8, PYDEM_TA_COUNT = 9
+};
+int pydem_terrain_attributes(pydem_tile *t, int half_width /* k, 1..7 */,
+                             const double *light /* Le, Ln, Lu; may be NULL when no hillshade is asked */, double z_factor,
+                             double *const *outs /* PYDEM_TA_COUNT host planes [n,m]; NULL = not wanted */, double *ms,
+                             int64_t *n_defined);
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
 /* What the tile knows about its flats mask against its slopes, and what the pydem_find_flats calls on it have launched so far

@@ -89,6 +89,7 @@ SYMBOLS = {
                                     C.POINTER(C.c_int64), _P]),
     'pydem_depressions_table': (C.c_int, [_P, C.c_int64, _P]),
     'pydem_hand_table': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    'pydem_terrain_attributes': (C.c_int, [_P, C.c_int, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'pydem_pit_candidates': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'pydem_pit_candidates_read': (C.c_int, [_P, C.c_int64, _P, _P]),
     'pydem_pit_paths': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
@@ -467,6 +468,23 @@ class Tile(object):
         check(self.lib.pydem_hand_table(self._h, _ptr(zone), _ptr(h), _ptr(st), st.size, K, _ptr(ints), _ptr(skipped), _ptr(quanta),
                                         _ptr(ms)))
         return ints, skipped, tuple(float(v) for v in quanta), dict(zip(self.HAND_TABLE_PARTS, ms.tolist()))
+
+    # enum pydem_terrain_attr, in its order
+    TERRAIN_ATTRS = ('dzdx', 'dzdy', 'gradient', 'aspect', 'profile', 'plan', 'tangential', 'mean', 'hillshade')
+
+    def terrain_attributes(self, which, half_width, light=None, z_factor=1.0, out=None):
+        """pydem_terrain_attributes: ({name: float64 [n, m]} for the names in `which`, device ms, defined cells).  light: the unit
+        vector to the sun (east, north, up), needed for 'hillshade'; out: {name: array} to fill instead of new arrays (C-contiguous
+        float64 of the tile's shape).  The library checks the rest (HipError -2)."""
+        planes = {nm: np.empty(self.shape, np.float64) if out is None else out[nm] for nm in which}
+        for nm, a in planes.items():
+            if a.shape != self.shape or a.dtype != np.float64 or not a.flags.c_contiguous:
+                raise ValueError("plane %r must be a C-contiguous float64 array of shape %r" % (nm, self.shape))
+        outs = (C.c_void_p * len(self.TERRAIN_ATTRS))(*[planes[nm].ctypes.data if nm in planes else None for nm in self.TERRAIN_ATTRS])
+        lv = None if light is None else np.ascontiguousarray(light, np.float64).reshape(3)
+        ms, count = C.c_double(0), C.c_int64(0)
+        check(self.lib.pydem_terrain_attributes(self._h, int(half_width), _ptr(lv), float(z_factor), outs, C.byref(ms), C.byref(count)))
+        return planes, ms.value, int(count.value)
 
     def pit_drain_paths(self, below_sea, max_iter, max_dist, max_dist_XY, sort_dtype=None):
         """calc_pit_drain_paths on the resident elevation.  Returns (n_failed, iterations used, rounds), or None when the tile

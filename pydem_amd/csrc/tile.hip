@@ -605,6 +605,15 @@ int pydem_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, con
     return stage_hand_table(t, zone, hand, stages, n_stages, n_zones, table, skipped, quanta, ms);
 }
 
+int pydem_terrain_attributes(pydem_tile *t, int half_width, const double *light, double z_factor, double *const *outs, double *ms,
+                             int64_t *n_defined)
+{
+    if (!t) { pydem_set_error("pydem_terrain_attributes: no tile"); return -2; }
+    HIP_TRY(hipSetDevice(t->device));
+    // reads the elevation and the spacing: no field, flag or timing changes
+    return stage_terrain_attributes(t, half_width, light, z_factor, outs, ms, n_defined);
+}
+
 int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
 {
     HIP_TRY(hipSetDevice(t->device));

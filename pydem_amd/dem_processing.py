@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _ffi
 from .flow_analyses import FlowAnalyses, _refuse_drain_alternatives
+from .terrain import TerrainAnalyses
 
 logger = logging.getLogger(__name__)
 
@@ -57,9 +58,10 @@ class _Resident(object):
             obj._host[self.name] = np.asarray(value)
 
 
-class DEMProcessor(FlowAnalyses):
+class DEMProcessor(FlowAnalyses, TerrainAnalyses):
     """Slope magnitude, D-infinity direction, upstream contributing area and TWI of one DEM tile; the analyses on its flow graph
-    (calc_weighted_uca ... calc_reach_attributes) are flow_analyses.FlowAnalyses."""
+    (calc_weighted_uca ... calc_reach_attributes) are flow_analyses.FlowAnalyses, the windowed terrain attributes
+    (calc_terrain_attributes, calc_curvature, calc_hillshade) terrain.TerrainAnalyses."""
 
     # ---- options: names and defaults of the reference (dem_processing.py:105-154) ----
     fill_flats = True
