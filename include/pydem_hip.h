@@ -38,6 +38,8 @@
  *                             pass, fixed-point sums under integer atomics) -- no reference method
  *   pydem_terrain_attributes  gradient, aspect, profile / plan / tangential / mean curvature and hillshade of the resident elevation from
  *                             a least-squares quadratic over a (2k+1)^2 window (Evans 1980, Wood 1996) -- no reference method
+ *   pydem_horizon             the horizon tangent per azimuth and the sky-view factor of the resident elevation along nearest-cell
+ *                             rays of a host-built table (cast shadows follow on the host) -- no reference method
  *   pydem_twi                 DEMProcessor.calc_twi               pydem/dem_processing.py:1647-1677
  *
  * Ownership: the caller owns every host buffer it passes; the library owns device memory behind
@@ -424,6 +426,52 @@ int pydem_terrain_attributes(pydem_tile *t, int half_width /* k, 1..7 */,
                              const double *light /* Le, Ln, Lu; may be NULL when no hillshade is asked */, double z_factor,
                              double *const *outs /* PYDEM_TA_COUNT host planes [n,m]; NULL = not wanted */, double *ms,
                              int64_t *n_defined);
+/* Horizon and sky-view factor of the resident float64 elevation: what the terrain around a cell hides from it; no reference method.
+ * pydem_terrain_attributes describes the surface inside a window of at most 15 cells; this call looks along rays of up to 1024 cells.
+ * A horizon tangent is the maximum of a fixed set of products and the sky-view factor a fixed sequence of * + /, none contracted and
+ * the division correctly rounded, so the host twin (pydem_amd/horizon.py: horizon_ref) gives the same bits.
+ * RAY TABLE, built on the host (pydem_amd/horizon.py: ray_table) so that the device and the twin read the same integers and doubles.
+ * One cell size gx x gy holds for the whole call (the caller takes dX2 / dY2 of the tile's middle row: exact on projected tiles, an
+ * approximation on geographic ones).  Direction d = 0 .. n_dir - 1 has the azimuth a_d = azimuth0 + d * 360 / n_dir degrees
+ * clockwise from north; rows grow to the south, columns to the east.  Its ground direction (sin a, cos a) (east, north) becomes the
+ * index-space direction (sc, sr) = (sin a / gx, -cos a / gy), scaled so that max(|sr|, |sc|) == 1.  Step k = 1, 2, ... samples the
+ * cell (dr_k, dc_k) = (round(k * sr), round(k * sc)), halves rounded away from zero, at the distance of that cell's centre,
+ * dist_k = sqrt((dc_k * gx)^2 + (dr_k * gy)^2); steps are kept while dist_k <= max_dist, at most 1024 per direction, and
+ * w_k = z_factor / dist_k.  start[n_dir + 1] (int32, start[0] == 0): direction d owns the steps start[d] .. start[d + 1] - 1 of
+ * dr, dc (int16) and w (float64).  A direction without a step is legal; its tangent is 0.
+ * DEFINITION, for a cell (r, c) with z0 = elev[r, c] not NaN, and a direction d:
+ *     T_d = 0.0
+ *     for every step k of d whose sample (r + dr_k, c + dc_k) lies inside the tile:
+ *         v = (elev[r + dr_k, c + dc_k] - z0) * w_k         one subtraction, one multiplication
+ *         if v > T_d: T_d = v                               a NaN sample compares false: no data does not obstruct
+ *   T_d >= 0 is the tangent of the horizon's elevation angle; the horizon is never below the horizontal.  The set of v is fixed by
+ *   the table, so every sample order gives the same bits.  A cell with NaN elevation is NaN (0x7ff8000000000000) in every plane.
+ *   With edge_nan, T_d is NaN wherever any sample of d's steps falls outside the tile: a finite value is a complete one.  Without,
+ *   samples off the tile are skipped.
+ *   svf = (sum over d of 1.0 / (1.0 + T_d * T_d)) / (double)n_dir, the sum started at 0.0 and added in ascending d: the mean of
+ *   cos^2 of the horizon angle, NaN if any T_d is NaN.
+ *   *n_defined: the cells with a finite svf; when no svf is asked for, the cells whose T_d are all finite.  Counted with an integer
+ *   reduction across the wavefront and integer atomics spread over 64 words.
+ * ARGUMENTS.  n_dir 1 .. 64.  horizon: n_dir host planes [n,m] of float64 (the tangents), or NULL; svf: a host plane [n,m], or
+ * NULL; only what is asked for is downloaded.  *ms: device time of the kernels (a hipEvent pair).  -2 (before anything is
+ * allocated, launched or written) for n_dir outside 1 .. 64, a missing table array, neither horizon nor svf, a NULL among the
+ * horizon planes, start[0] != 0, a direction with fewer than 0 or more than 1024 steps, a weight that is not finite, not > 0 or above
+ * the one before it in its direction, and a segment (at most 32 consecutive steps of a direction) whose row or column offsets span more than 32 cells
+ * (no ray does: an offset moves by at most one cell per step); -3 without a spacing or an elevation.
+ * KERNEL (csrc/horizon.hip).  A workgroup of four wavefronts owns 32 rows x 64 columns, a lane per column and eight rows per lane,
+ * with z0, T_d and the svf sum in registers.  It walks a ray in segments of at most 32 steps: the source region of a segment --
+ * the block shifted by the segment's offsets, at most 64 x 96 doubles (49 664 bytes of LDS), cells off the tile as NaN -- is staged in LDS,
+ * and every lane takes its samples from there.  A launch takes consecutive directions of at most 512 steps in all (one direction at
+ * least); the svf sum passes from launch to launch through its plane, in ascending d on one stream, so the additions keep their
+ * order.
+ * MEMORY.  One device block of the tile: 8192 bytes, the table (16 bytes per step, a segment's steps padded to a multiple of 4, and 32 per segment and direction, each part
+ * rounded up to 256), 8 n m bytes for the svf sum (held whether svf is asked for or not) and 8 n m bytes per direction when the
+ * horizon planes are asked for; grown to the largest request so far, counted by pydem_tile_device_bytes and freed with the tile.
+ * Reads the elevation; needs no slope, flats or flow graph.  Writes no field of the tile, no timing and no state of any other
+ * analysis. */
+int pydem_horizon(pydem_tile *t, int n_dir /* 1..64 */, const int32_t *start /* [n_dir+1] */, const int16_t *dr, const int16_t *dc,
+                  const double *w /* [start[n_dir]] each */, int edge_nan, double *const *horizon /* n_dir host planes [n,m], or NULL */,
+                  double *svf /* host plane [n,m], or NULL */, double *ms, int64_t *n_defined);
 int pydem_slopes_directions(pydem_tile *t);
 int pydem_find_flats(pydem_tile *t);
 /* What the tile knows about its flats mask against its slopes, and what the pydem_find_flats calls on it have launched so far

@@ -90,6 +90,7 @@ SYMBOLS = {
     'pydem_depressions_table': (C.c_int, [_P, C.c_int64, _P]),
     'pydem_hand_table': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     'pydem_terrain_attributes': (C.c_int, [_P, C.c_int, _P, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'pydem_horizon': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'pydem_pit_candidates': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'pydem_pit_candidates_read': (C.c_int, [_P, C.c_int64, _P, _P]),
     'pydem_pit_paths': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
@@ -484,6 +485,31 @@ class Tile(object):
         lv = None if light is None else np.ascontiguousarray(light, np.float64).reshape(3)
         ms, count = C.c_double(0), C.c_int64(0)
         check(self.lib.pydem_terrain_attributes(self._h, int(half_width), _ptr(lv), float(z_factor), outs, C.byref(ms), C.byref(count)))
+        return planes, ms.value, int(count.value)
+
+    def horizon(self, table, edge_nan=True, want_horizon=False, want_svf=True, out=None):
+        """pydem_horizon: ({'horizon': float64 [n_dir, n, m] tangents, 'svf': float64 [n, m]} as asked for, device ms, defined
+        cells).  table: a horizon.RayTable (start int32 [n_dir + 1], dr / dc int16, w float64); out: {name: array} to fill instead
+        of new arrays (C-contiguous float64).  The library checks the rest (HipError -2)."""
+        start = np.ascontiguousarray(table.start, np.int32)
+        dr, dc = np.ascontiguousarray(table.dr, np.int16), np.ascontiguousarray(table.dc, np.int16)
+        w = np.ascontiguousarray(table.w, np.float64)
+        n_dir = int(start.size) - 1
+        if n_dir < 1 or not (dr.size == dc.size == w.size) or (start.size and int(start[-1]) != w.size):
+            raise ValueError("the ray table's arrays do not fit together")
+        shapes = {}
+        if want_horizon:
+            shapes['horizon'] = (n_dir,) + self.shape
+        if want_svf:
+            shapes['svf'] = self.shape
+        planes = {nm: np.empty(shp, np.float64) if out is None else out[nm] for nm, shp in shapes.items()}
+        for nm, a in planes.items():
+            if a.shape != shapes[nm] or a.dtype != np.float64 or not a.flags.c_contiguous:
+                raise ValueError("plane %r must be a C-contiguous float64 array of shape %r" % (nm, shapes[nm]))
+        hor = (C.c_void_p * n_dir)(*[planes['horizon'][d].ctypes.data for d in range(n_dir)]) if want_horizon else None
+        ms, count = C.c_double(0), C.c_int64(0)
+        check(self.lib.pydem_horizon(self._h, n_dir, _ptr(start), _ptr(dr), _ptr(dc), _ptr(w), int(bool(edge_nan)), hor,
+                                     _ptr(planes.get('svf')), C.byref(ms), C.byref(count)))
         return planes, ms.value, int(count.value)
 
     def pit_drain_paths(self, below_sea, max_iter, max_dist, max_dist_XY, sort_dtype=None):

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libpydem_hip.so')
-SOURCES = ['tile.hip', 'devmem.hip', 'stencil.hip', 'flats.hip', 'uca.hip', 'uca_edge.hip', 'flowdist.hip', 'flowdist_up.hip', 'flowacc_rev.hip', 'flowacc_fwd.hip', 'streamnet.hip', 'flowacc_tree.hip', 'pits.hip', 'synth.hip', 'comm.hip', 'cyutils.hip', 'cond_host.cpp', 'tiff_lzw.cpp', 'cond_device.hip', 'cond_paths.hip', 'fill_depressions.hip', 'depressions.hip', 'hand_table.hip', 'terrain.hip']
+SOURCES = ['tile.hip', 'devmem.hip', 'stencil.hip', 'flats.hip', 'uca.hip', 'uca_edge.hip', 'flowdist.hip', 'flowdist_up.hip', 'flowacc_rev.hip', 'flowacc_fwd.hip', 'streamnet.hip', 'flowacc_tree.hip', 'pits.hip', 'synth.hip', 'comm.hip', 'cyutils.hip', 'cond_host.cpp', 'tiff_lzw.cpp', 'cond_device.hip', 'cond_paths.hip', 'fill_depressions.hip', 'depressions.hip', 'hand_table.hip', 'terrain.hip', 'horizon.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-fno-fast-math',
          '-Wall', '-Wno-unused-function', '-Wno-unused-result']

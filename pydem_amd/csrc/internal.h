@@ -145,6 +145,9 @@ struct pydem_tile {
     bool dd_down_ready = false;
     // pydem_terrain_attributes (terrain.hip): its counter and the planes of one call, grown to the largest request, freed with the tile
     void *ta_mem = nullptr; size_t ta_bytes = 0;
+    // pydem_horizon (horizon.hip): its counter, the ray table, the svf plane and the horizon planes of one call, grown to the largest
+    // request, freed with the tile
+    void *hz_mem = nullptr; size_t hz_bytes = 0;
     void *scratch = nullptr; size_t scratch_bytes = 0;
     // pydem_fill_seam_* (fill_depressions.hip), one session at a time: W of the open session (a plane), the flag words of its
     // 32 x 32 blocks and its cap lines (top m, bottom m, left n, right n doubles; +inf: no cap), all three held from begin to end;
@@ -256,6 +259,8 @@ int stage_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, con
                      int64_t *table, int64_t *skipped, double *quanta, double *ms);
 int stage_terrain_attributes(pydem_tile *t, int half_width, const double *light, double z_factor, double *const *outs, double *ms,
                              int64_t *n_defined);
+int stage_horizon(pydem_tile *t, int n_dir, const int32_t *start, const int16_t *dr, const int16_t *dc, const double *w, int edge_nan,
+                  double *const *horizon, double *svf, double *ms, int64_t *n_defined);
 int stage_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits);
 int stage_pit_candidates_read(pydem_tile *t, int64_t npits, int32_t *cells, double *elev);
 int stage_pit_paths(pydem_tile *t, const int32_t *order_host, int64_t npits, int max_iter, int max_dist, double max_dist_XY,

@@ -614,6 +614,15 @@ int pydem_terrain_attributes(pydem_tile *t, int half_width, const double *light,
     return stage_terrain_attributes(t, half_width, light, z_factor, outs, ms, n_defined);
 }
 
+int pydem_horizon(pydem_tile *t, int n_dir, const int32_t *start, const int16_t *dr, const int16_t *dc, const double *w, int edge_nan,
+                  double *const *horizon, double *svf, double *ms, int64_t *n_defined)
+{
+    if (!t) { pydem_set_error("pydem_horizon: no tile"); return -2; }
+    HIP_TRY(hipSetDevice(t->device));
+    // reads the elevation: no field, flag or timing changes
+    return stage_horizon(t, n_dir, start, dr, dc, w, edge_nan, horizon, svf, ms, n_defined);
+}
+
 int pydem_pit_candidates(pydem_tile *t, int below_sea, int64_t *npits)
 {
     HIP_TRY(hipSetDevice(t->device));

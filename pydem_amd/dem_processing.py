@@ -19,6 +19,7 @@ import numpy as np
 from . import _ffi
 from .flow_analyses import FlowAnalyses, _refuse_drain_alternatives
 from .terrain import TerrainAnalyses
+from .horizon import HorizonAnalyses
 
 logger = logging.getLogger(__name__)
 
@@ -58,10 +59,11 @@ class _Resident(object):
             obj._host[self.name] = np.asarray(value)
 
 
-class DEMProcessor(FlowAnalyses, TerrainAnalyses):
+class DEMProcessor(FlowAnalyses, TerrainAnalyses, HorizonAnalyses):
     """Slope magnitude, D-infinity direction, upstream contributing area and TWI of one DEM tile; the analyses on its flow graph
     (calc_weighted_uca ... calc_reach_attributes) are flow_analyses.FlowAnalyses, the windowed terrain attributes
-    (calc_terrain_attributes, calc_curvature, calc_hillshade) terrain.TerrainAnalyses."""
+    (calc_terrain_attributes, calc_curvature, calc_hillshade) terrain.TerrainAnalyses, the horizon, sky-view factor and cast shadows
+    (calc_horizon, calc_sky_view_factor, calc_cast_shadow, calc_shaded_relief) horizon.HorizonAnalyses."""
 
     # ---- options: names and defaults of the reference (dem_processing.py:105-154) ----
     fill_flats = True
