@@ -69,7 +69,9 @@ __device__ __forceinline__ void facet(double s1, double s2, double sd, double d1
 // ocml's general atan2 costs ~130 fp64 operations per cell -- more than a quarter of the whole
 // stencil; this one is ~45: q = min/max in (0, 1], c = nearest multiple of 1/16,
 // atan(q) = atan(c) + atan(u), u = (q - c)/(1 + q*c), |u| <= 1/32, odd Taylor series to u^11
-// (truncation < 1e-19 relative), table of correctly rounded atan(k/16).  Error <= ~1.5 ulp.
+// (truncation < 1e-19 relative), table of correctly rounded atan(k/16).  Error <= ~1.5 ulp of the result: 1.35 measured on
+// the designed ratios of tests/stencil_fields.py (both sides of every switch of the table entry, with and without the swap,
+// slopes from 2^-470 to 2^470), which tests/test_gpu_stencil_bits.py holds to 2 ulp on every path of this file.
 __device__ __constant__ const double ATAN_16[17] = {
     0, 0.06241880999595735, 0.12435499454676144, 0.18534794999569476, 0.24497866312686414, 0.30288486837497142,
     0.35877067027057225, 0.41241044159738732, 0.46364760900080609, 0.51238946031073773, 0.55859931534356244,
@@ -133,7 +135,8 @@ __device__ __forceinline__ void facet_lean(double s1, double s2, double sd, doub
 
 // x / d for a per-row spacing d with r = RN(1/d) from the host: q = RN(x*r), one exact remainder, one
 // correction -- Markstein's sequence returns the correctly rounded quotient (checked against 4e8
-// IEEE divisions on the host, oracle/ and tests compare the results bit for bit), 3 full-rate
+// IEEE divisions on the host; tests/test_gpu_stencil_bits.py compares magnitudes that are one such quotient, by spacings
+// whose reciprocals round badly, with numpy's bit for bit -- the other tests only to 1e-11), 3 full-rate
 // operations instead of ~11 with a quarter-rate v_rcp_f64
 __device__ __forceinline__ double div_row(double x, double d, double r)
 {
@@ -299,7 +302,10 @@ __device__ __forceinline__ double pick(lmask m, double a, double b) { return ON(
 
 // IEEE division u = a / b for the arctangent's reduced argument, 0 <= a, 0 < b with b within a factor 2 of the larger
 // slope: reciprocal seed + two Newton steps + Markstein's residual correction (correctly rounded like `/`; without the
-// exponent rescue of the generic expansion, which slopes cannot need: |slope| in [2^-500, 2^500] by the window test)
+// exponent rescue of the generic expansion).  The window test bounds elevations (< 2^500) and spacings (2^-500 .. 2^500), NOT
+// slopes: all it guarantees here is that a and b are finite.  The sequence needs more -- the reciprocal, the Newton residuals
+// and the last remainder (about 2^-53 a) must stay normal -- which slopes within [2^-480, 2^480] leave ample room for; that
+// is the range tests/test_gpu_stencil_bits.py holds to the bit and to 2 ulp.  Nothing is promised for slopes outside it.
 __device__ __forceinline__ double div_pos(double a, double b)
 {
 #ifdef PYDEM_STENCIL_CHEAP
@@ -315,9 +321,11 @@ __device__ __forceinline__ double div_pos(double a, double b)
     return __builtin_fma(rem, y, q);
 }
 
-// sqrt(x) for x in [2^-1000, 2^1000] (squared slopes: the window test keeps the slopes within 2^+-500): the compiler's
-// correctly rounded expansion (reciprocal square root seed, Goldschmidt step, two residual corrections) without the
-// exponent scaling and the zero / infinity special cases it wraps around it
+// sqrt(x) for the squares of slopes within [2^-480, 2^480] (tests/test_gpu_stencil_bits.py: numpy's bits there): the compiler's
+// correctly rounded expansion (reciprocal square root seed, Goldschmidt step, two residual corrections) without the exponent
+// scaling and the zero / infinity special cases it wraps around it.  The window test bounds elevations and spacings, not
+// slopes: a far smaller square loses the last place (its residuals go subnormal), and +inf -- the square of a slope next to a
+// huge elevation, which the exact path does meet -- would come out as NaN (rsq(inf) = 0, times inf): mag_of() keeps it away
 __device__ __forceinline__ double sqrt_window(double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -328,6 +336,13 @@ __device__ __forceinline__ double sqrt_window(double x)
     g = __builtin_fma(d, h, g);
     d = __builtin_fma(-g, g, x);
     return __builtin_fma(d, h, g);
+}
+
+// the magnitude a cell stores (:1901): the root of a positive finite square; -1 (no facet descends), 0, NaN and +inf (the
+// reference's sqrt(inf) = inf) as they are.  One v_cmp_class instead of the v_cmp_gt of `M > 0`.
+__device__ __forceinline__ double mag_of(double M)
+{
+    return __builtin_amdgcn_class(M, 0x180) ? sqrt_window(M) : M;      // 0x180: +normal | +subnormal
 }
 
 __device__ __forceinline__ double atan2_pos_fast(double y, double x, const double *atan_16)
@@ -588,11 +603,11 @@ __device__ __forceinline__ void march_band(const MarchCtx &cx, BandCarry &c, con
         if (SPLIT) {
             StoreRing &R = *cx.ring;
             const int slot = (b - cx.i0) & (SR_ROWS - 1);
-            R.mag[slot][lane] = M > 0 ? sqrt_window(M) : M;
+            R.mag[slot][lane] = mag_of(M);
             R.dir[slot][lane] = pick(flat, -1.0, direction);
             R.flat[slot][lane] = ON(flat) ? 1 : 0;
         } else {
-        cx.mag[cc] = M > 0 ? sqrt_window(M) : M;                       // :1901
+        cx.mag[cc] = mag_of(M);                                        // :1901
 #endif
         cx.dir[cc] = pick(flat, -1.0, direction);
         cx.flat0[cc] = ON(flat) ? 1 : 0;
