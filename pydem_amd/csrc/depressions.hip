@@ -21,18 +21,17 @@
 //   k_dp_flatten  parent = root; the root of a component is its smallest linear index whatever the order of the unions, since
 //                 the cell with that index can never be linked below itself.  Flags the roots for the scan.
 // Numbering: hipcub exclusive scan of the root flags in place: rank of a root = depressions with a smaller first cell.  K is the
-// last word of the scan: the last cell of the tile is a border cell, never raised.  k_dp_ids then turns the parent plane into the
-// plane of ids 1..K (0 not raised, -1 no data) and stores each depression's level from its root cell.
-// Statistics: k_dp_stats, one lane per cell.  Raised cells: the lanes of a wavefront that share an id reduce across the wavefront
-// (xor shuffles) and their first lane issues the atomics -- one set per wavefront inside a large lake instead of 64.  Other
-// finite cells look at their eight neighbours for the sill columns and drop duplicate ids in registers.  k_dp_bottom finds the
-// smallest index among the cells at a depression's lowest z; k_dp_botelev copies that cell's elevation.
+// last word of the scan, and one more when the last cell is a root (label_components).  k_dp_ids then turns the parent plane into
+// the plane of ids 1..K (0 not raised, -1 no data) and stores each depression's level from its root cell.
+// Statistics: k_dp_stats, one lane per cell.  Raised cells (dp_raised): the lanes of a wavefront that share a row reduce across the
+// wavefront (wave_by_key of stage_kit.h) and their first lane issues the atomics -- one set per wavefront inside a large lake
+// instead of 64.  Other finite cells look at their eight neighbours for the sill columns and drop duplicate rows in registers
+// (dp_sills).  k_dp_bottom finds the smallest index among the cells at a depression's lowest z; k_dp_botelev copies that cell's
+// elevation.
 // The table is K rows of DT_COLS 64-bit words, column-major, in the conditioning arena; the host filters it, uploads the
 // id -> kept id lookup, and k_dp_write produces the label plane.
-#include "internal.h"
+#include "stage_kit.h"
 #include <hipcub/hipcub.hpp>
-#include <math.h>
-#include <string.h>
 #include <memory>
 
 namespace {
@@ -45,15 +44,17 @@ constexpr int DP_R = DP_B * DP_B / DP_T;
 enum { DPC_DEPTH = 0,   // bits of max (W - z)
        DPC_WORDS = 8 };
 
-// table columns (64-bit words, column c of depression k at tab[c * K + k])
+// table columns (64-bit words, column c of row k at tab[c * T + k]).  The first DT_SEAM_COLS, in this order, are the partial table
+// of pydem_fill_seam_inventory: its ABI, mirrored by conditioning.SEAM_TABLE_COLS.  The table of pydem_depressions has the level
+// too; the host reads it column by column (col() of stage_depressions), so the order is nobody's business there.
 enum { DT_CELLS = 0, DT_R0, DT_R1, DT_C0, DT_C1,
        DT_ZMIN,         // order-preserving pattern of the lowest z (+0.0 for -0.0: they compare equal)
        DT_BOTTOM, DT_POUR, DT_NSILLS, DT_OPEN,
        DT_AREA, DT_VOLUME,      // fixed-point sums (int64 in two's complement; every term is >= 0)
-       DT_SPILL, DT_BOTELEV,    // bits of doubles, plain stores
+       DT_BOTELEV,              // bits of a double, a plain store
+       DT_SEAM_COLS,
+       DT_SPILL = DT_SEAM_COLS, // the same
        DT_COLS };
-
-typedef unsigned long long u64;
 
 __device__ inline int dp_ld(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -105,7 +106,7 @@ k_dp_init(const double *__restrict__ z, const double *__restrict__ W, int32_t *_
         parent[c] = up ? (int32_t)c : -1;
         if (up && w - v > dmax) dmax = w - v;
     }
-    for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(dmax, o); dmax = u > dmax ? u : dmax; }
+    dmax = wave_max(dmax);
     if ((threadIdx.x & 63) == 0 && dmax > 0.0) atomicMax(ctr + DPC_DEPTH, (u64)__double_as_longlong(dmax));
 }
 
@@ -202,12 +203,13 @@ k_dp_flatten(int32_t *parent, int32_t *__restrict__ rank, int64_t NN)
     }
 }
 
+// the first `cols` columns of a table of T rows
 __global__ void __launch_bounds__(256)
-k_dp_table_init(u64 *tab, int64_t K)
+k_dp_table_init(u64 *tab, int64_t T, int cols)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= K * DT_COLS) return;
-    const int col = (int)(i / K);
+    if (i >= T * cols) return;
+    const int col = (int)(i / T);
     const bool is_min = col == DT_R0 || col == DT_C0 || col == DT_ZMIN || col == DT_BOTTOM || col == DT_POUR;
     tab[i] = is_min ? ~0ull : 0ull;
 }
@@ -229,17 +231,81 @@ k_dp_ids(int32_t *lab, const int32_t *__restrict__ rank, const double *__restric
     }
 }
 
-__device__ inline int dp_wave_min(int v) { for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o)); return v; }
-__device__ inline int dp_wave_max(int v) { for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o)); return v; }
-__device__ inline u64 dp_wave_min(u64 v) { for (int o = 32; o > 0; o >>= 1) { const u64 u = __shfl_xor(v, o); v = u < v ? u : v; } return v; }
-__device__ inline u64 dp_wave_add(u64 v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+// The statistics of a raised cell (up) of row `row` (1 .. T) at (r, q): elevation zc, surface wc, cell area a0.  The lanes of the
+// wavefront that share the row publish one set of atomics into eight columns.  Reached by the whole wavefront.
+__device__ __forceinline__ void dp_raised(bool up, int row, int r, int q, double zc, double wc, double a0, int sh_area, int sh_vol,
+                                          u64 *tab, int64_t T)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    u64 zk = ~0ull, ai = 0, vi = 0;
+    if (up) {
+        zk = dp_key(zc + 0.0);
+        ai = (u64)__double2ll_rn(ldexp(a0, sh_area));
+        vi = (u64)__double2ll_rn(ldexp((wc - zc) * a0, sh_vol));
+    }
+    wave_by_key(up, row, [&](int lrow, int leader, u64 mask, bool mine, bool lone) {
+        int rmin = r, rmax = r, qmin = q, qmax = q;
+        u64 cnt = 1, k = zk, a = ai, v = vi;
+        if (!lone) {                                        // more than one lane: reduce first (uniform branch)
+            rmin = wave_min(mine ? r : 0x7fffffff);
+            rmax = wave_max(mine ? r : -1);
+            qmin = wave_min(mine ? q : 0x7fffffff);
+            qmax = wave_max(mine ? q : -1);
+            k = wave_min(mine ? zk : ~0ull);
+            a = wave_add(mine ? ai : 0ull);
+            v = wave_add(mine ? vi : 0ull);
+            cnt = (u64)__popcll(mask);
+        }
+        if (lane == leader) {
+            u64 *w = tab + (lrow - 1);
+            atomicAdd(w + (int64_t)DT_CELLS * T, cnt);
+            atomicMin(w + (int64_t)DT_R0 * T, (u64)rmin);
+            atomicMax(w + (int64_t)DT_R1 * T, (u64)rmax);
+            atomicMin(w + (int64_t)DT_C0 * T, (u64)qmin);
+            atomicMax(w + (int64_t)DT_C1 * T, (u64)qmax);
+            atomicMin(w + (int64_t)DT_ZMIN * T, k);
+            atomicAdd(w + (int64_t)DT_AREA * T, a);
+            atomicAdd(w + (int64_t)DT_VOLUME * T, v);
+        }
+    });
+}
 
+// neighbour j = 0 .. 7 of a cell, row by row
+__device__ __forceinline__ void dp_neighbour(int j, int r, int q, int &rr, int &qq)
+{
+    rr = r + (j < 3 ? -1 : (j < 5 ? 0 : 1));
+    qq = q + (j < 3 ? j - 1 : (j == 3 ? -1 : (j == 4 ? 1 : j - 6)));
+}
+
+// A sill cell c -- finite, not raised, beside a depression whose level is its elevation: rows[j] is the row of neighbour j where
+// that neighbour is such a depression's cell, else 0.  Every distinct row gets the cell once (duplicates dropped in registers).
+__device__ __forceinline__ void dp_sills(const int (&rows)[8], bool open, const uint8_t *__restrict__ outlets, int64_t c, u64 *tab, int64_t T)
+{
+    int found = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) found |= rows[j];
+    if (!found) return;
+    if (outlets && outlets[c] != 0) open = true;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        bool fresh = rows[j] > 0;
+#pragma unroll
+        for (int i = 0; i < j; i++) fresh = fresh && rows[i] != rows[j];
+        if (fresh) {
+            u64 *w = tab + (rows[j] - 1);
+            atomicAdd(w + (int64_t)DT_NSILLS * T, 1ull);
+            atomicMin(w + (int64_t)DT_POUR * T, (u64)c);
+            if (open) atomicMax(w + (int64_t)DT_OPEN * T, 1ull);
+        }
+    }
+}
+
+// rows are the ids of the plane; a neighbour outside the tile is nothing (its cell is on the border: open)
 __global__ void __launch_bounds__(256)
 k_dp_stats(const int32_t *__restrict__ lab, const double *__restrict__ z, const double *__restrict__ W, const uint8_t *__restrict__ outlets,
            const double *__restrict__ dX2, const double *__restrict__ dY2, u64 *tab, int64_t K, int n, int m, int sh_area, int sh_vol)
 {
     const int64_t NN = (int64_t)n * m;
-    const int lane = (int)(threadIdx.x & 63);
     for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < NN; c0 += (int64_t)gridDim.x * blockDim.x) {     // (uniform per wavefront)
         const int64_t c = c0 + threadIdx.x;
         int id = 0, r = 0, q = 0;
@@ -251,76 +317,22 @@ k_dp_stats(const int32_t *__restrict__ lab, const double *__restrict__ z, const 
             zc = z[c];
         }
         const bool up = id > 0 && id <= K;
-        u64 zk = ~0ull, ai = 0, vi = 0;
-        if (up) {
-            const double a0 = dX2[r] * dY2[r];                  // row_area (k_row_area)
-            zk = dp_key(zc + 0.0);
-            ai = (u64)__double2ll_rn(ldexp(a0, sh_area));
-            vi = (u64)__double2ll_rn(ldexp((W[c] - zc) * a0, sh_vol));
-        }
-        u64 todo = __ballot(up);
-        while (todo) {                                          // (todo is the same in every lane)
-            const int leader = __ffsll((long long)todo) - 1;
-            const int lid = __shfl(id, leader);
-            const bool mine = up && id == lid;
-            const u64 mask = __ballot(mine);
-            todo &= ~mask;
-            int rmin = r, rmax = r, qmin = q, qmax = q;
-            u64 cnt = 1, k = zk, a = ai, v = vi;
-            if (mask != (1ull << leader)) {                     // more than one lane: reduce first (uniform branch)
-                rmin = dp_wave_min(mine ? r : 0x7fffffff);
-                rmax = dp_wave_max(mine ? r : -1);
-                qmin = dp_wave_min(mine ? q : 0x7fffffff);
-                qmax = dp_wave_max(mine ? q : -1);
-                k = dp_wave_min(mine ? zk : ~0ull);
-                a = dp_wave_add(mine ? ai : 0ull);
-                v = dp_wave_add(mine ? vi : 0ull);
-                cnt = (u64)__popcll(mask);
-            }
-            if (lane == leader) {
-                u64 *row = tab + (lid - 1);
-                atomicAdd(row + (int64_t)DT_CELLS * K, cnt);
-                atomicMin(row + (int64_t)DT_R0 * K, (u64)rmin);
-                atomicMax(row + (int64_t)DT_R1 * K, (u64)rmax);
-                atomicMin(row + (int64_t)DT_C0 * K, (u64)qmin);
-                atomicMax(row + (int64_t)DT_C1 * K, (u64)qmax);
-                atomicMin(row + (int64_t)DT_ZMIN * K, k);
-                atomicAdd(row + (int64_t)DT_AREA * K, a);
-                atomicAdd(row + (int64_t)DT_VOLUME * K, v);
-            }
-        }
-        // sills: a finite cell that is not raised, beside a depression whose level is this cell's elevation
+        dp_raised(up, id, r, q, zc, up ? W[c] : 0.0, up ? dX2[r] * dY2[r] : 0.0, sh_area, sh_vol, tab, K);      // (row_area, as k_row_area)
         if (c < NN && id == 0) {
-            int ids[8];
+            int rows[8];
             bool open = r == 0 || r == n - 1 || q == 0 || q == m - 1;
-            int found = 0;
 #pragma unroll
             for (int j = 0; j < 8; j++) {
-                const int dr = j < 3 ? -1 : (j < 5 ? 0 : 1);
-                const int dq = j < 3 ? j - 1 : (j == 3 ? -1 : (j == 4 ? 1 : j - 6));
-                const int rr = r + dr, qq = q + dq;
-                ids[j] = 0;
+                int rr, qq;
+                dp_neighbour(j, r, q, rr, qq);
+                rows[j] = 0;
                 if (rr < 0 || rr >= n || qq < 0 || qq >= m) continue;
                 const int64_t v = (int64_t)rr * m + qq;
                 const int l = lab[v];
                 if (l < 0) open = true;                         // beside no data
-                else if (l > 0 && l <= K && W[v] == zc) { ids[j] = l; found = 1; }
+                else if (l > 0 && l <= K && W[v] == zc) rows[j] = l;
             }
-            if (found) {
-                if (outlets && outlets[c] != 0) open = true;
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    bool fresh = ids[j] > 0;
-#pragma unroll
-                    for (int i = 0; i < j; i++) fresh = fresh && ids[i] != ids[j];
-                    if (fresh) {
-                        u64 *row = tab + (ids[j] - 1);
-                        atomicAdd(row + (int64_t)DT_NSILLS * K, 1ull);
-                        atomicMin(row + (int64_t)DT_POUR * K, (u64)c);
-                        if (open) atomicMax(row + (int64_t)DT_OPEN * K, 1ull);
-                    }
-                }
-            }
+            dp_sills(rows, open, outlets, c, tab, K);
         }
     }
 }
@@ -336,12 +348,12 @@ k_dp_bottom(const int32_t *__restrict__ lab, const double *__restrict__ z, u64 *
 }
 
 __global__ void __launch_bounds__(256)
-k_dp_botelev(const double *__restrict__ z, u64 *tab, int64_t K, int64_t NN)
+k_dp_botelev(const double *__restrict__ z, u64 *tab, int64_t T, int64_t NN)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= K) return;
-    const u64 b = tab[(int64_t)DT_BOTTOM * K + k];
-    if (b < (u64)NN) tab[(int64_t)DT_BOTELEV * K + k] = (u64)__double_as_longlong(z[b]);
+    if (k >= T) return;
+    const u64 b = tab[(int64_t)DT_BOTTOM * T + k];
+    if (b < (u64)NN) tab[(int64_t)DT_BOTELEV * T + k] = (u64)__double_as_longlong(z[b]);
 }
 
 __global__ void __launch_bounds__(256)
@@ -353,30 +365,51 @@ k_dp_write(const int32_t *__restrict__ lab, const int32_t *__restrict__ lut, int
     }
 }
 
-double as_double(u64 b)
+// The labelling of the raised cells (W > z): parent <- each cell's root, the smallest linear index of its component (-1: not
+// raised); out->rank <- the exclusive scan of the root flags; K components; depth_max the largest W - z.  rank, the counter block
+// and the scan's scratch come from the lease.  ev_start is recorded where the device work begins; marks (may be null): marks[0],
+// [1], [2] after init + local, merge, flatten.  Waits for the stream.
+struct Labelling { int32_t *rank = nullptr; int64_t K = 0; double depth_max = 0.0; };
+int label_components(pydem_tile *t, ArenaLease *lease, const char *who, const double *W, int32_t *parent, hipEvent_t ev_start,
+                     hipEvent_t *marks, Labelling *out)
 {
-    double d;
-    ::memcpy(&d, &b, 8);
-    return d;
-}
-
-struct Events {
-    hipEvent_t e[10] = {};
-    int n = 0;
-    ~Events() { for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]); }
-};
-
-// fraction bits and exponent of the fixed-point sums: B = min(40, 62 - ceil(log2(max(cells, 2)))), E from frexp of the largest term
-void fixed_point(int64_t cells, double largest, int *shift, double *quantum)
-{
-    int lg = 0;
-    const uint64_t x = (uint64_t)(cells < 2 ? 2 : cells) - 1;
-    while (lg < 64 && (x >> lg)) lg++;                  // ceil(log2(x + 1))
-    const int B = 62 - lg < 40 ? 62 - lg : 40;
-    int E = 0;
-    (void)frexp(largest, &E);
-    *shift = B - E;
-    *quantum = ldexp(1.0, E - B);
+    const bool local = env_switch("PYDEM_DEPR_LOCAL", true);    // read per call: the tests switch it
+    const int n = (int)t->n, m = (int)t->m;
+    const int64_t NN = t->NN;
+    int32_t *rank = (int32_t *)arena_take(lease, (size_t)NN * 4);
+    u64 *ctr = (u64 *)arena_take(lease, DPC_WORDS * 8);
+    size_t scan_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)NN, t->stream));
+    void *scan_tmp = arena_take(lease, scan_bytes);
+    if (!rank || !ctr || !scan_tmp) return -1;
+    const int gfull = capped_grid(NN, GRID_FULL);
+    HIP_TRY(hipEventRecord(ev_start, t->stream));
+    HIP_TRY(hipMemsetAsync(ctr, 0, DPC_WORDS * 8, t->stream));
+    hipLaunchKernelGGL(k_dp_init, dim3(capped_grid(NN, GRID_LOOP)), dim3(256), 0, t->stream, (const double *)t->elev, W, parent, NN, ctr);
+    if (local) hipLaunchKernelGGL(k_dp_local, dim3((unsigned)cdiv(m, DP_B), (unsigned)cdiv(n, DP_B)), dim3(DP_T), 0, t->stream, parent, n, m);
+    HIP_TRY(hipGetLastError());
+    if (marks) HIP_TRY(hipEventRecord(marks[0], t->stream));
+    hipLaunchKernelGGL(k_dp_merge, dim3(gfull), dim3(256), 0, t->stream, parent, n, m, local ? 0 : 1);
+    HIP_TRY(hipGetLastError());
+    if (marks) HIP_TRY(hipEventRecord(marks[1], t->stream));
+    hipLaunchKernelGGL(k_dp_flatten, dim3(gfull), dim3(256), 0, t->stream, parent, rank, NN);
+    HIP_TRY(hipGetLastError());
+    if (marks) HIP_TRY(hipEventRecord(marks[2], t->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, rank, rank, (int)NN, t->stream));
+    // K and the largest depth.  The exclusive sum at the last cell leaves that cell out: it counts when it is its own root.  A seam
+    // cell of a session may be raised, the tile's last cell included; in pydem_depressions the last cell is an open border cell
+    // and never a root, so the rule gives the plain last word of the scan there.
+    volatile u64 *h = (volatile u64 *)t->h_counters;
+    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, 8, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_counters + 2, rank + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_counters + 3, parent + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    const int64_t K = (int64_t)t->h_counters[2] + ((int64_t)t->h_counters[3] == NN - 1 ? 1 : 0);
+    if (K < 0 || K > NN) { pydem_set_error("%s: inconsistent count of depressions (%lld)", who, (long long)K); return -5; }
+    out->rank = rank;
+    out->K = K;
+    out->depth_max = as_double(h[DPC_DEPTH]);
+    return 0;
 }
 
 }  // namespace
@@ -390,13 +423,11 @@ int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
     }
     if (!t->spacing_set) { pydem_set_error("pydem_depressions: call pydem_tile_set_spacing first"); return -3; }
     if (t->NN >= (int64_t)INT32_MAX) { pydem_set_error("pydem_depressions: %lld cells do not fit the int32 parent plane", (long long)t->NN); return -2; }
-    const char *e = getenv("PYDEM_DEPR_LOCAL");                 // read per call: the tests switch it
-    const bool local = !(e && *e && atoi(e) == 0);
     const int n = (int)t->n, m = (int)t->m;
     const int64_t NN = t->NN;
 
-    Events ev;
-    for (; ev.n < 9; ev.n++) HIP_TRY(hipEventCreate(&ev.e[ev.n]));
+    Events<9> ev;
+    PYDEM_TRY(ev.create());
     ArenaLease lease;
     PYDEM_TRY(arena_acquire(t->device, &lease));
     FillRelax fr;
@@ -405,36 +436,13 @@ int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
     const double *W = fr.W;
     const double *z = t->elev;
     int32_t *parent = (int32_t *)arena_take(&lease, (size_t)NN * 4);
-    int32_t *rank = (int32_t *)arena_take(&lease, (size_t)NN * 4);
-    u64 *ctr = (u64 *)arena_take(&lease, DPC_WORDS * 8);
-    size_t scan_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)NN, t->stream));
-    void *scan_tmp = arena_take(&lease, scan_bytes);
-    if (!parent || !rank || !ctr || !scan_tmp) return -1;
-
-    const int gcells = (int)(cdiv(NN, 256) < 8192 ? cdiv(NN, 256) : 8192);
-    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
-    HIP_TRY(hipEventRecord(ev.e[1], t->stream));                // relaxation done
-    HIP_TRY(hipMemsetAsync(ctr, 0, DPC_WORDS * 8, t->stream));
-    hipLaunchKernelGGL(k_dp_init, dim3(gcells), dim3(256), 0, t->stream, z, W, parent, NN, ctr);
-    if (local) hipLaunchKernelGGL(k_dp_local, dim3((unsigned)cdiv(m, DP_B), (unsigned)cdiv(n, DP_B)), dim3(DP_T), 0, t->stream, parent, n, m);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e[2], t->stream));
-    hipLaunchKernelGGL(k_dp_merge, dim3(gfull), dim3(256), 0, t->stream, parent, n, m, local ? 0 : 1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e[3], t->stream));
-    hipLaunchKernelGGL(k_dp_flatten, dim3(gfull), dim3(256), 0, t->stream, parent, rank, NN);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e[4], t->stream));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, rank, rank, (int)NN, t->stream));
-    // K and the largest depth
-    volatile u64 *h = (volatile u64 *)t->h_counters;
-    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, 8, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipMemcpyAsync(t->h_counters + 2, rank + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    const double depth_max = as_double(h[DPC_DEPTH]);
-    const int64_t K = (int64_t)t->h_counters[2];        // (the last cell lies on the border: it is no root, so the exclusive sum there is the total)
-    if (K < 0 || K > NN) { pydem_set_error("pydem_depressions: inconsistent count of depressions (%lld)", (long long)K); return -5; }
+    if (!parent) return -1;
+    Labelling lb;
+    PYDEM_TRY(label_components(t, &lease, "pydem_depressions", W, parent, ev.e[1], &ev.e[2], &lb));    // (ev.e[1]: relaxation done)
+    int32_t *rank = lb.rank;
+    const int64_t K = lb.K;
+    const double depth_max = lb.depth_max;
+    const int gcells = capped_grid(NN, GRID_LOOP), gfull = capped_grid(NN, GRID_FULL);
 
     double amax = 0.0;
     for (int64_t r = 0; r < t->n; r++) { const double a = t->h_dX2[(size_t)r] * t->h_dY2[(size_t)r]; if (a > amax) amax = a; }
@@ -453,7 +461,7 @@ int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
                             (long long)K, (long long)(K * (DT_COLS * 8 + 4)));
             return -6;
         }
-        hipLaunchKernelGGL(k_dp_table_init, dim3((unsigned)cdiv(K * DT_COLS, 256)), dim3(256), 0, t->stream, tab, K);
+        hipLaunchKernelGGL(k_dp_table_init, dim3((unsigned)cdiv(K * DT_COLS, 256)), dim3(256), 0, t->stream, tab, K, (int)DT_COLS);
     }
     hipLaunchKernelGGL(k_dp_ids, dim3(gfull), dim3(256), 0, t->stream, parent, (const int32_t *)rank, W, tab, K, NN);
     HIP_TRY(hipGetLastError());
@@ -513,11 +521,7 @@ int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
     if (ms) {
         // whole call, relaxation, init + local, merge, flatten, numbering, statistics, table (download, host filter, lookup upload), label write
         static const int from[9] = {0, 0, 1, 2, 3, 4, 5, 6, 8}, to[9] = {7, 1, 2, 3, 4, 5, 6, 8, 7};
-        for (int i = 0; i < 9; i++) {
-            float el = 0.f;
-            HIP_TRY(hipEventElapsedTime(&el, ev.e[from[i]], ev.e[to[i]]));
-            ms[i] = (double)el;
-        }
+        for (int i = 0; i < 9; i++) PYDEM_TRY(ev.elapsed(from[i], to[i], &ms[i]));
     }
     if (n_found) *n_found = K;
     if (n_kept) *n_kept = (int64_t)rows.size();
@@ -534,9 +538,6 @@ int stage_depressions(pydem_tile *t, const uint8_t *outlets, double min_depth, i
 // (2 m + 2 n + 4 cells: the row above over columns -1 .. m, the row below, the column left over rows 0 .. n-1, the column right).
 // Integers only, as above: the host twin (conditioning.SeamFill) gives the same words.
 namespace {
-
-// the partial table: S_COLS columns of n_rows 64-bit words, column-major
-enum { S_CELLS = 0, S_R0, S_R1, S_C0, S_C1, S_ZMIN, S_BOTTOM, S_POUR, S_NSILLS, S_OPEN, S_AREA, S_VOLUME, S_BOTELEV, S_COLS };
 
 // parent (flattened) -> local ids in place, as k_dp_ids; a root stores its cell and its level
 __global__ void __launch_bounds__(256)
@@ -556,30 +557,15 @@ k_ds_ids(int32_t *lab, const int32_t *__restrict__ rank, const double *__restric
     }
 }
 
-__global__ void __launch_bounds__(256)
-k_ds_gather(const int32_t *__restrict__ src, int64_t pitch, int64_t cnt, int32_t *__restrict__ dst)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i * pitch];
-}
-
-__global__ void __launch_bounds__(256)
-k_ds_table_init(u64 *tab, int64_t T)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T * S_COLS) return;
-    const int col = (int)(i / T);
-    const bool is_min = col == S_R0 || col == S_C0 || col == S_ZMIN || col == S_BOTTOM || col == S_POUR;
-    tab[i] = is_min ? ~0ull : 0ull;
-}
-
-// k_dp_stats on the cells the tile owns, with rows through the lookup (several local ids may share a row) and the halo ring
+// k_dp_stats on the cells the tile owns: rows through the lookup (several local ids may share a row), and a neighbour outside the
+// window from the halo ring.  A sill's whole 3 x 3 is known here, so it is open exactly when a neighbour is no data or uncovered
+// (-1), or when it is an outlet
 __global__ void __launch_bounds__(256)
 k_ds_stats(const int32_t *__restrict__ ids, const double *__restrict__ z, const double *__restrict__ W, const uint8_t *__restrict__ outlets,
            const uint8_t *__restrict__ owner, const int32_t *__restrict__ lut, const int32_t *__restrict__ halo_ids,
            const double *__restrict__ halo_W, const double *__restrict__ row_area, u64 *tab, int64_t T, int n, int m, int sh_area, int sh_vol)
 {
     const int64_t NN = (int64_t)n * m;
-    const int lane = (int)(threadIdx.x & 63);
     for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < NN; c0 += (int64_t)gridDim.x * blockDim.x) {     // (uniform per wavefront)
         const int64_t c = c0 + threadIdx.x;
         int l = -1, g = 0, r = 0, q = 0;
@@ -594,56 +580,15 @@ k_ds_stats(const int32_t *__restrict__ ids, const double *__restrict__ z, const 
             if (l > 0) g = lut[l];
         }
         const bool up = own && g > 0;
-        u64 zk = ~0ull, ai = 0, vi = 0;
-        if (up) {
-            const double a0 = row_area[r];
-            zk = dp_key(zc + 0.0);
-            ai = (u64)__double2ll_rn(ldexp(a0, sh_area));
-            vi = (u64)__double2ll_rn(ldexp((W[c] - zc) * a0, sh_vol));
-        }
-        u64 todo = __ballot(up);
-        while (todo) {                                          // (todo is the same in every lane)
-            const int leader = __ffsll((long long)todo) - 1;
-            const int lid = __shfl(g, leader);
-            const bool mine = up && g == lid;
-            const u64 mask = __ballot(mine);
-            todo &= ~mask;
-            int rmin = r, rmax = r, qmin = q, qmax = q;
-            u64 cnt = 1, k = zk, a = ai, v = vi;
-            if (mask != (1ull << leader)) {                     // more than one lane: reduce first (uniform branch)
-                rmin = dp_wave_min(mine ? r : 0x7fffffff);
-                rmax = dp_wave_max(mine ? r : -1);
-                qmin = dp_wave_min(mine ? q : 0x7fffffff);
-                qmax = dp_wave_max(mine ? q : -1);
-                k = dp_wave_min(mine ? zk : ~0ull);
-                a = dp_wave_add(mine ? ai : 0ull);
-                v = dp_wave_add(mine ? vi : 0ull);
-                cnt = (u64)__popcll(mask);
-            }
-            if (lane == leader) {
-                u64 *row = tab + (lid - 1);
-                atomicAdd(row + (int64_t)S_CELLS * T, cnt);
-                atomicMin(row + (int64_t)S_R0 * T, (u64)rmin);
-                atomicMax(row + (int64_t)S_R1 * T, (u64)rmax);
-                atomicMin(row + (int64_t)S_C0 * T, (u64)qmin);
-                atomicMax(row + (int64_t)S_C1 * T, (u64)qmax);
-                atomicMin(row + (int64_t)S_ZMIN * T, k);
-                atomicAdd(row + (int64_t)S_AREA * T, a);
-                atomicAdd(row + (int64_t)S_VOLUME * T, v);
-            }
-        }
-        // sills: an owned finite cell that is not raised, beside a depression whose level is this cell's elevation; its whole 3 x 3
-        // is known here, so it is open exactly when a neighbour is no data or uncovered (-1), or when it is an outlet
+        dp_raised(up, g, r, q, zc, up ? W[c] : 0.0, up ? row_area[r] : 0.0, sh_area, sh_vol, tab, T);
         if (c < NN && own && l == 0) {
-            int gs[8];
+            int rows[8];
             bool open = false;
-            int found = 0;
 #pragma unroll
             for (int j = 0; j < 8; j++) {
-                const int dr = j < 3 ? -1 : (j < 5 ? 0 : 1);
-                const int dq = j < 3 ? j - 1 : (j == 3 ? -1 : (j == 4 ? 1 : j - 6));
-                const int rr = r + dr, qq = q + dq;
-                gs[j] = 0;
+                int rr, qq;
+                dp_neighbour(j, r, q, rr, qq);
+                rows[j] = 0;
                 int gv;
                 double wv = 0.0;
                 if (rr >= 0 && rr < n && qq >= 0 && qq < m) {
@@ -661,23 +606,9 @@ k_ds_stats(const int32_t *__restrict__ ids, const double *__restrict__ z, const 
                     wv = halo_W[h];
                 }
                 if (gv < 0) open = true;
-                else if (gv > 0 && wv == zc) { gs[j] = gv; found = 1; }
+                else if (gv > 0 && wv == zc) rows[j] = gv;
             }
-            if (found) {
-                if (outlets && outlets[c] != 0) open = true;
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    bool fresh = gs[j] > 0;
-#pragma unroll
-                    for (int i = 0; i < j; i++) fresh = fresh && gs[i] != gs[j];
-                    if (fresh) {
-                        u64 *row = tab + (gs[j] - 1);
-                        atomicAdd(row + (int64_t)S_NSILLS * T, 1ull);
-                        atomicMin(row + (int64_t)S_POUR * T, (u64)c);
-                        if (open) atomicMax(row + (int64_t)S_OPEN * T, 1ull);
-                    }
-                }
-            }
+            dp_sills(rows, open, outlets, c, tab, T);
         }
     }
 }
@@ -691,17 +622,8 @@ k_ds_bottom(const int32_t *__restrict__ ids, const double *__restrict__ z, const
         if (l <= 0 || owner[c] == 0) continue;
         const int g = lut[l];
         if (g <= 0) continue;
-        if (z[c] == dp_unkey(tab[(int64_t)S_ZMIN * T + g - 1])) atomicMin(tab + (int64_t)S_BOTTOM * T + g - 1, (u64)c);
+        if (z[c] == dp_unkey(tab[(int64_t)DT_ZMIN * T + g - 1])) atomicMin(tab + (int64_t)DT_BOTTOM * T + g - 1, (u64)c);
     }
-}
-
-__global__ void __launch_bounds__(256)
-k_ds_botelev(const double *__restrict__ z, u64 *tab, int64_t T, int64_t NN)
-{
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= T) return;
-    const u64 b = tab[(int64_t)S_BOTTOM * T + k];
-    if (b < (u64)NN) tab[(int64_t)S_BOTELEV * T + k] = (u64)__double_as_longlong(z[b]);
 }
 
 __global__ void __launch_bounds__(256)
@@ -713,16 +635,6 @@ k_ds_write(const int32_t *__restrict__ ids, const int32_t *__restrict__ lut, int
     }
 }
 
-int seam_elapsed(pydem_tile *t, double *ms)
-{
-    HIP_TRY(hipEventRecord(t->ev[7], t->stream));
-    HIP_TRY(hipEventSynchronize(t->ev[7]));
-    float el = 0.f;
-    HIP_TRY(hipEventElapsedTime(&el, t->ev[6], t->ev[7]));
-    if (ms) *ms = (double)el;
-    return 0;
-}
-
 }  // namespace
 
 int stage_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, double *ms)
@@ -730,9 +642,6 @@ int stage_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, do
     const char *who = "pydem_fill_seam_label";
     if (!t->fs_open) { pydem_set_error("%s: no session is open on this tile (pydem_fill_seam_begin first)", who); return -2; }
     if (t->NN >= (int64_t)INT32_MAX) { pydem_set_error("%s: %lld cells do not fit the int32 id plane", who, (long long)t->NN); return -2; }
-    const char *e = getenv("PYDEM_DEPR_LOCAL");                 // read per call: the tests switch it
-    const bool local = !(e && *e && atoi(e) == 0);
-    const int n = (int)t->n, m = (int)t->m;
     const int64_t NN = t->NN;
     if (!t->fs_ids) PYDEM_TRY(tile_hold(t, (void **)&t->fs_ids, (size_t)NN * 4, true));
     t->fs_K = -1;
@@ -742,33 +651,12 @@ int stage_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, do
     ArenaLease lease;
     PYDEM_TRY(arena_acquire(t->device, &lease));
     int32_t *parent = t->fs_ids;
-    int32_t *rank = (int32_t *)arena_take(&lease, (size_t)NN * 4);
-    u64 *ctr = (u64 *)arena_take(&lease, DPC_WORDS * 8);
-    size_t scan_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)NN, t->stream));
-    void *scan_tmp = arena_take(&lease, scan_bytes);
-    if (!rank || !ctr || !scan_tmp) return -1;
     const double *W = t->fs_W;
-    const double *z = t->elev;
-    const int gcells = (int)(cdiv(NN, 256) < 8192 ? cdiv(NN, 256) : 8192);
-    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
-    HIP_TRY(hipEventRecord(t->ev[6], t->stream));
-    HIP_TRY(hipMemsetAsync(ctr, 0, DPC_WORDS * 8, t->stream));
-    hipLaunchKernelGGL(k_dp_init, dim3(gcells), dim3(256), 0, t->stream, z, W, parent, NN, ctr);
-    if (local) hipLaunchKernelGGL(k_dp_local, dim3((unsigned)cdiv(m, DP_B), (unsigned)cdiv(n, DP_B)), dim3(DP_T), 0, t->stream, parent, n, m);
-    hipLaunchKernelGGL(k_dp_merge, dim3(gfull), dim3(256), 0, t->stream, parent, n, m, local ? 0 : 1);
-    hipLaunchKernelGGL(k_dp_flatten, dim3(gfull), dim3(256), 0, t->stream, parent, rank, NN);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, rank, rank, (int)NN, t->stream));
-    // K and the largest depth.  A seam cell may be raised, the tile's last cell included: it counts when it is its own root
-    volatile u64 *h = (volatile u64 *)t->h_counters;
-    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, 8, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipMemcpyAsync(t->h_counters + 2, rank + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipMemcpyAsync(t->h_counters + 3, parent + (NN - 1), 4, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    const double depth_max = as_double(h[DPC_DEPTH]);
-    const int64_t K = (int64_t)t->h_counters[2] + ((int64_t)t->h_counters[3] == NN - 1 ? 1 : 0);
-    if (K < 0 || K > NN) { pydem_set_error("%s: inconsistent count of depressions (%lld)", who, (long long)K); return -5; }
+    Labelling lb;
+    PYDEM_TRY(label_components(t, &lease, who, W, parent, t->ev[6], nullptr, &lb));
+    const int32_t *rank = lb.rank;
+    const int64_t K = lb.K;
+    const double depth_max = lb.depth_max;
     if (!std::isfinite(depth_max)) {
         pydem_set_error("%s: cells of W are still +inf (no relaxation has reached them); nothing was labelled", who);
         return -5;
@@ -780,9 +668,9 @@ int stage_fill_seam_label(pydem_tile *t, int64_t *n_local, double *max_depth, do
         levels = (double *)arena_take(&lease, (size_t)K * 8);
         if (!roots || !levels) return -1;
     }
-    hipLaunchKernelGGL(k_ds_ids, dim3(gfull), dim3(256), 0, t->stream, parent, (const int32_t *)rank, W, roots, levels, K, NN);
+    hipLaunchKernelGGL(k_ds_ids, dim3(capped_grid(NN, GRID_FULL)), dim3(256), 0, t->stream, parent, (const int32_t *)rank, W, roots, levels, K, NN);
     HIP_TRY(hipGetLastError());
-    PYDEM_TRY(seam_elapsed(t, ms));
+    PYDEM_TRY(stage_elapsed(t, ms));
     if (K > 0) {
         t->fs_roots.resize((size_t)K);
         t->fs_levels.resize((size_t)K);
@@ -814,41 +702,7 @@ int stage_fill_seam_get_id_lines(pydem_tile *t, int count, const int *axes, cons
 {
     const char *who = "pydem_fill_seam_get_id_lines";
     if (!t->fs_open || t->fs_K < 0) { pydem_set_error("%s: the open session has no labels (pydem_fill_seam_label first)", who); return -2; }
-    if (count <= 0) return 0;
-    const size_t Lmax = (size_t)(t->n > t->m ? t->n : t->m);
-    int ncols = 0;
-    for (int k = 0; k < count; k++) {
-        const int64_t lim = axes[k] == 0 ? t->n : t->m;
-        if ((axes[k] != 0 && axes[k] != 1) || indices[k] < -lim || indices[k] >= lim) { pydem_set_error("%s: line index out of range", who); return -2; }
-        if (axes[k] == 1) ncols++;
-    }
-    ArenaLease lease;
-    int32_t *stage = nullptr;
-    if (ncols) {
-        PYDEM_TRY(arena_acquire(t->device, &lease));
-        stage = (int32_t *)arena_take(&lease, (size_t)ncols * (size_t)t->n * 4);
-        if (!stage) return -1;
-    }
-    void *pin_v = nullptr;
-    PYDEM_TRY(tile_pinned(t, (size_t)count * Lmax * 4, &pin_v));
-    char *pin = (char *)pin_v;
-    int col = 0;
-    for (int k = 0; k < count; k++) {
-        const int64_t lim = axes[k] == 0 ? t->n : t->m;
-        const int64_t index = indices[k] < 0 ? indices[k] + lim : indices[k];
-        if (axes[k] == 0) {
-            HIP_TRY(hipMemcpyAsync(pin + (size_t)k * Lmax * 4, t->fs_ids + (size_t)index * t->m, (size_t)t->m * 4, hipMemcpyDeviceToHost, t->stream));
-        } else {
-            int32_t *dst = stage + (size_t)col++ * (size_t)t->n;
-            const int g = (int)(cdiv(t->n, 256) < 64 ? cdiv(t->n, 256) : 64);
-            hipLaunchKernelGGL(k_ds_gather, dim3(g), dim3(256), 0, t->stream, (const int32_t *)(t->fs_ids + index), t->m, t->n, dst);
-            HIP_TRY(hipMemcpyAsync(pin + (size_t)k * Lmax * 4, dst, (size_t)t->n * 4, hipMemcpyDeviceToHost, t->stream));
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    for (int k = 0; k < count; k++) memcpy(dsts[k], pin + (size_t)k * Lmax * 4, (size_t)(axes[k] == 0 ? t->m : t->n) * 4);
-    return 0;
+    return seam_get_lines(t, who, (const int32_t *)t->fs_ids, count, axes, indices, dsts);
 }
 
 int stage_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t T, const uint8_t *owner, const uint8_t *outlets,
@@ -878,7 +732,7 @@ int stage_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t T, cons
     int32_t *d_hid = (int32_t *)arena_take(&lease, R * 4);
     double *d_hW = (double *)arena_take(&lease, R * 8);
     double *d_ra = (double *)arena_take(&lease, (size_t)n * 8);
-    u64 *tab = (u64 *)arena_take(&lease, (size_t)T * S_COLS * 8);
+    u64 *tab = (u64 *)arena_take(&lease, (size_t)T * DT_SEAM_COLS * 8);
     if (!d_lut || !d_owner || (outlets && !d_out) || !d_hid || !d_hW || !d_ra || !tab) return -1;
     PYDEM_TRY(tile_plane_copy(t, d_lut, const_cast<int32_t *>(lut), (size_t)(K + 1) * 4, false));
     PYDEM_TRY(tile_plane_copy(t, d_owner, const_cast<uint8_t *>(owner), (size_t)NN, false));
@@ -887,20 +741,19 @@ int stage_fill_seam_inventory(pydem_tile *t, const int32_t *lut, int64_t T, cons
     PYDEM_TRY(tile_plane_copy(t, d_hW, const_cast<double *>(halo_W), R * 8, false));
     PYDEM_TRY(tile_plane_copy(t, d_ra, const_cast<double *>(row_area), (size_t)n * 8, false));
 
-    const int gcells = (int)(cdiv(NN, 256) < 8192 ? cdiv(NN, 256) : 8192);
-    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
+    const int gcells = capped_grid(NN, GRID_LOOP), gfull = capped_grid(NN, GRID_FULL);
     const double *z = t->elev;
     HIP_TRY(hipEventRecord(t->ev[6], t->stream));
-    hipLaunchKernelGGL(k_ds_table_init, dim3((unsigned)cdiv(T * S_COLS, 256)), dim3(256), 0, t->stream, tab, T);
+    hipLaunchKernelGGL(k_dp_table_init, dim3((unsigned)cdiv(T * DT_SEAM_COLS, 256)), dim3(256), 0, t->stream, tab, T, (int)DT_SEAM_COLS);
     hipLaunchKernelGGL(k_ds_stats, dim3(gcells), dim3(256), 0, t->stream, (const int32_t *)t->fs_ids, z, (const double *)t->fs_W,
                        (const uint8_t *)d_out, (const uint8_t *)d_owner, (const int32_t *)d_lut, (const int32_t *)d_hid, (const double *)d_hW,
                        (const double *)d_ra, tab, T, n, m, sh_area, sh_vol);
     hipLaunchKernelGGL(k_ds_bottom, dim3(gfull), dim3(256), 0, t->stream, (const int32_t *)t->fs_ids, z, (const uint8_t *)d_owner,
                        (const int32_t *)d_lut, tab, T, NN);
-    hipLaunchKernelGGL(k_ds_botelev, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, t->stream, z, tab, T, NN);
+    hipLaunchKernelGGL(k_dp_botelev, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, t->stream, z, tab, T, NN);
     HIP_TRY(hipGetLastError());
-    PYDEM_TRY(seam_elapsed(t, ms));
-    PYDEM_TRY(tile_plane_copy(t, tab, table, (size_t)T * S_COLS * 8, true));
+    PYDEM_TRY(stage_elapsed(t, ms));
+    PYDEM_TRY(tile_plane_copy(t, tab, table, (size_t)T * DT_SEAM_COLS * 8, true));
     return 0;
 }
 
@@ -916,11 +769,11 @@ int stage_fill_seam_labels(pydem_tile *t, const int32_t *lut, int32_t *label, do
     int32_t *out = (int32_t *)arena_take(&lease, (size_t)NN * 4);
     if (!d_lut || !out) return -1;
     PYDEM_TRY(tile_plane_copy(t, d_lut, const_cast<int32_t *>(lut), (size_t)(K + 1) * 4, false));
-    const int gfull = (int)(cdiv(NN, 256) < (1 << 20) ? cdiv(NN, 256) : (1 << 20));
+    const int gfull = capped_grid(NN, GRID_FULL);
     HIP_TRY(hipEventRecord(t->ev[6], t->stream));
     hipLaunchKernelGGL(k_ds_write, dim3(gfull), dim3(256), 0, t->stream, (const int32_t *)t->fs_ids, (const int32_t *)d_lut, out, NN);
     HIP_TRY(hipGetLastError());
-    PYDEM_TRY(seam_elapsed(t, ms));
+    PYDEM_TRY(stage_elapsed(t, ms));
     PYDEM_TRY(tile_plane_copy(t, out, label, (size_t)NN * 4, true));
     return 0;
 }

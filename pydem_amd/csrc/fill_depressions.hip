@@ -28,9 +28,7 @@
 // tiles' values, W = max(z, min(cap, min (W[v] + eps))).  Still monotone, in W and in the caps, so W at a fixed point is a valid
 // start when caps fall.  Its visit is a second instantiation of the same body (SEAM): the lane's four caps in registers, one fmin
 // more per update, 82 VGPRs and 5 wavefronts per SIMD (profiles/fill_mosaic_cost.txt); the plain one compiles the cap out.
-#include "internal.h"
-#include <math.h>
-#include <string.h>
+#include "stage_kit.h"
 
 namespace {
 
@@ -48,12 +46,6 @@ enum { FD_AMAX = 0,     // bits of max |z| over the finite cells (non-negative d
        FD_LOWERED = 5,  // seam session: cells whose W is lower than the snapshot of the call's start
        FD_LEFT = 6,     // seam session: cells of W that are still +inf
        FD_WORDS = 8 };
-
-__device__ inline double fd_wave_max(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(v, o); v = u > v ? u : v; }
-    return v;
-}
 
 // W0 = z on open cells, +inf on the other finite cells, NaN kept; max |z| and the +-inf test into the counter block
 // SEAM (the session): a border cell marked in `seam` (top m, bottom m, left n, right n bytes) is not open by position
@@ -90,7 +82,7 @@ k_fd_init(const double *__restrict__ z, const uint8_t *__restrict__ outlets, dou
         }
         W[c] = open ? v : (double)INFINITY;
     }
-    amax = fd_wave_max(amax);
+    amax = wave_max(amax);
     const unsigned long long any_inf = __ballot(inf != 0);
     if ((threadIdx.x & 63) == 0) {
         if (amax > 0.0) atomicMax(ctr + FD_AMAX, (unsigned long long)__double_as_longlong(amax));
@@ -261,13 +253,6 @@ k_fs_count(const double *__restrict__ W, const double *__restrict__ before, int6
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(ctr + word, cnt);
 }
 
-// column `src[0], src[pitch], ...` of a plane into a contiguous line
-__global__ void __launch_bounds__(256)
-k_fs_gather(const double *__restrict__ src, int64_t pitch, int64_t cnt, double *__restrict__ dst)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i * pitch];
-}
-
 // depth = W - z (into the W plane), raised cells, maximum depth, elev = W
 __global__ void __launch_bounds__(256)
 k_fd_final(double *__restrict__ z, double *__restrict__ W, int64_t NN, unsigned long long *ctr)
@@ -286,24 +271,11 @@ k_fd_final(double *__restrict__ z, double *__restrict__ W, int64_t NN, unsigned 
         }
         cnt += (unsigned long long)__popcll(__ballot(up));
     }
-    dmax = fd_wave_max(dmax);
+    dmax = wave_max(dmax);
     if ((threadIdx.x & 63) == 0) {
         if (cnt) atomicAdd(ctr + FD_RAISED, cnt);
         if (dmax > 0.0) atomicMax(ctr + FD_DEPTH, (unsigned long long)__double_as_longlong(dmax));
     }
-}
-
-double as_double(unsigned long long b)
-{
-    double d;
-    ::memcpy(&d, &b, 8);
-    return d;
-}
-
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
 }
 
 // read per call: the tests switch them
@@ -312,7 +284,7 @@ int fill_env(const char *who, FillEnv *e)
 {
     e->max_passes = env_int("PYDEM_FILL_MAX_PASSES", 100000);
     if (e->max_passes < 1) { pydem_set_error("%s: PYDEM_FILL_MAX_PASSES must be >= 1", who); return -2; }
-    e->local = env_int("PYDEM_FILL_LOCAL", 1) != 0;
+    e->local = env_switch("PYDEM_FILL_LOCAL", true);
     e->every = env_int("PYDEM_FILL_CHECK_EVERY", 4);         // passes between two looks at the counter (the result does not depend on it)
     if (e->every < 1) e->every = 1;
     return 0;
@@ -389,7 +361,7 @@ int fill_relax(pydem_tile *t, ArenaLease *lease, const char *who, double *epsilo
 
     volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;     // (64 int32: room for the block)
     auto look = [&]() -> int { return fill_look(t, ctr); };
-    const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
+    const int gcells = capped_grid(t->NN, GRID_LOOP);
 
     if (ev_start) HIP_TRY(hipEventRecord(ev_start, t->stream));
     HIP_TRY(hipMemsetAsync(ctr, 0, FD_WORDS * 8, t->stream));
@@ -437,15 +409,11 @@ int stage_fill_depressions(pydem_tile *t, double *epsilon, const uint8_t *outlet
     unsigned long long *ctr = fr.ctr;
     volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;
     const double eps = *epsilon;
-    const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
+    const int gcells = capped_grid(t->NN, GRID_LOOP);
     hipLaunchKernelGGL(k_fd_final, dim3(gcells), dim3(256), 0, t->stream, t->elev, W, t->NN, ctr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, FD_WORDS * 8, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipEventRecord(t->ev[7], t->stream));
-    HIP_TRY(hipEventSynchronize(t->ev[7]));
-    float el = 0.f;
-    HIP_TRY(hipEventElapsedTime(&el, t->ev[6], t->ev[7]));
-    if (ms) *ms = (double)el;
+    PYDEM_TRY(stage_elapsed(t, ms));
     if (passes) *passes = fr.passes;
     if (n_raised) *n_raised = (int64_t)h[FD_RAISED];
     if (max_depth) *max_depth = as_double(h[FD_DEPTH]);
@@ -505,7 +473,7 @@ int stage_fill_seam_begin(pydem_tile *t, const uint8_t *outlets, const uint8_t *
         }
         unsigned long long *ctr = (unsigned long long *)t->counters;
         volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;
-        const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
+        const int gcells = capped_grid(t->NN, GRID_LOOP);
         HIP_TRY(hipMemcpyAsync(t->fs_caps, pc, L * 8, hipMemcpyHostToDevice, t->stream));
         HIP_TRY(hipMemcpyAsync(d_seam, ps, L, hipMemcpyHostToDevice, t->stream));
         HIP_TRY(hipMemsetAsync(ctr, 0, FD_WORDS * 8, t->stream));
@@ -570,8 +538,8 @@ int stage_fill_seam_relax(pydem_tile *t, double eps, const double *const caps[4]
     }
     unsigned long long *ctr = (unsigned long long *)t->counters;
     volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;
-    const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
-    const int gcaps = (int)(cdiv((int64_t)L, 256) < 64 ? cdiv((int64_t)L, 256) : 64);
+    const int gcells = capped_grid(t->NN, GRID_LOOP);
+    const int gcaps = capped_grid((int64_t)L, 64);
     HIP_TRY(hipEventRecord(t->ev[6], t->stream));
     HIP_TRY(hipMemsetAsync(ctr, 0, FD_WORDS * 8, t->stream));
     HIP_TRY(hipMemcpyAsync(incoming, pc, L * 8, hipMemcpyHostToDevice, t->stream));
@@ -592,11 +560,7 @@ int stage_fill_seam_relax(pydem_tile *t, double eps, const double *const caps[4]
     hipLaunchKernelGGL(k_fs_count, dim3(gcells), dim3(256), 0, t->stream, (const double *)t->fs_W, (const double *)before, t->NN, ctr, (int)FD_LOWERED);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(t->h_counters, ctr, FD_WORDS * 8, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipEventRecord(t->ev[7], t->stream));
-    HIP_TRY(hipEventSynchronize(t->ev[7]));
-    float el = 0.f;
-    HIP_TRY(hipEventElapsedTime(&el, t->ev[6], t->ev[7]));
-    if (ms) *ms = (double)el;
+    PYDEM_TRY(stage_elapsed(t, ms));
     if (passes_out) *passes_out = passes;
     if (n_lowered) *n_lowered = (int64_t)h[FD_LOWERED];
     return 0;
@@ -606,41 +570,7 @@ int stage_fill_seam_get_lines(pydem_tile *t, int count, const int *axes, const i
 {
     const char *who = "pydem_fill_seam_get_lines";
     if (!t->fs_open) { pydem_set_error("%s: no session is open on this tile", who); return -2; }
-    if (count <= 0) return 0;
-    const size_t Lmax = (size_t)(t->n > t->m ? t->n : t->m);
-    int ncols = 0;
-    for (int k = 0; k < count; k++) {
-        const int64_t lim = axes[k] == 0 ? t->n : t->m;
-        if ((axes[k] != 0 && axes[k] != 1) || indices[k] < -lim || indices[k] >= lim) { pydem_set_error("%s: line index out of range", who); return -2; }
-        if (axes[k] == 1) ncols++;
-    }
-    ArenaLease lease;
-    double *stage = nullptr;
-    if (ncols) {
-        PYDEM_TRY(arena_acquire(t->device, &lease));
-        stage = (double *)arena_take(&lease, (size_t)ncols * (size_t)t->n * 8);
-        if (!stage) return -1;
-    }
-    void *pin_v = nullptr;
-    PYDEM_TRY(tile_pinned(t, (size_t)count * Lmax * 8, &pin_v));
-    char *pin = (char *)pin_v;
-    int col = 0;
-    for (int k = 0; k < count; k++) {
-        const int64_t lim = axes[k] == 0 ? t->n : t->m;
-        const int64_t index = indices[k] < 0 ? indices[k] + lim : indices[k];
-        if (axes[k] == 0) {
-            HIP_TRY(hipMemcpyAsync(pin + (size_t)k * Lmax * 8, t->fs_W + (size_t)index * t->m, (size_t)t->m * 8, hipMemcpyDeviceToHost, t->stream));
-        } else {
-            double *dst = stage + (size_t)col++ * (size_t)t->n;
-            const int g = (int)(cdiv(t->n, 256) < 64 ? cdiv(t->n, 256) : 64);
-            hipLaunchKernelGGL(k_fs_gather, dim3(g), dim3(256), 0, t->stream, (const double *)(t->fs_W + index), t->m, t->n, dst);
-            HIP_TRY(hipMemcpyAsync(pin + (size_t)k * Lmax * 8, dst, (size_t)t->n * 8, hipMemcpyDeviceToHost, t->stream));
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    for (int k = 0; k < count; k++) memcpy(dsts[k], pin + (size_t)k * Lmax * 8, (size_t)(axes[k] == 0 ? t->m : t->n) * 8);
-    return 0;
+    return seam_get_lines(t, who, (const double *)t->fs_W, count, axes, indices, dsts);
 }
 
 int stage_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_raised, double *max_depth)
@@ -650,7 +580,7 @@ int stage_fill_seam_end(pydem_tile *t, int commit, double *depth, int64_t *n_rai
     if (!commit) { fill_seam_drop(t); return 0; }
     unsigned long long *ctr = (unsigned long long *)t->counters;
     volatile unsigned long long *h = (volatile unsigned long long *)t->h_counters;
-    const int gcells = (int)(cdiv(t->NN, 256) < 8192 ? cdiv(t->NN, 256) : 8192);
+    const int gcells = capped_grid(t->NN, GRID_LOOP);
     HIP_TRY(hipMemsetAsync(ctr, 0, FD_WORDS * 8, t->stream));
     hipLaunchKernelGGL(k_fs_count, dim3(gcells), dim3(256), 0, t->stream, (const double *)t->fs_W, (const double *)nullptr, t->NN, ctr, (int)FD_LEFT);
     HIP_TRY(hipGetLastError());

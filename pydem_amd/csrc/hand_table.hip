@@ -10,25 +10,18 @@
 //              with atomicMax on the bit patterns of the magnitudes -- non-negative doubles order like their words.
 //   k_ht_sum   one lane per cell.  The stages sit in LDS and a binary search gives the bin; the key of a counted cell is
 //              (zone - 1) * S + bin, that of a NaN / above-the-top cell K * S + (zone - 1) * 2 + {0, 1}.  A wavefront walks its
-//              distinct keys (__ballot, first lane, __shfl); the lanes of one key reduce with xor shuffles and their first lane
+//              distinct keys (wave_by_key of stage_kit.h); the lanes of one key reduce with xor shuffles and their first lane
 //              issues the atomics -- one set per wavefront inside a large catchment instead of 64.  A lone lane skips the
 //              reduction.  PYDEM_HANDTAB_LOCAL=0 (read once per process): no reduction, every lane issues its own atomics.
 // The table ([K, S, 4] words, then [K, 2]) and the uploaded planes are leased from the conditioning arena: nothing stays with
 // the tile.
-#include "internal.h"
-#include <math.h>
-#include <string.h>
+#include "stage_kit.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int HT_MAX_STAGES = 1024;
 // counter block, 64-bit words: bits of max p_a, max |p_m|, max p_b; the largest zone id met (0: none above 0)
 enum { HTC_A = 0, HTC_M, HTC_B, HTC_ZONE, HTC_WORDS };
-
-__device__ inline u64 ht_wave_max(u64 v) { for (int o = 32; o > 0; o >>= 1) { const u64 u = __shfl_xor(v, o); v = u > v ? u : v; } return v; }
-__device__ inline u64 ht_wave_add(u64 v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
 
 // the three terms of a cell of row area a, HAND h and slope mg (a non-finite slope counts as 0)
 __device__ inline void ht_terms(double a, double h, double mg, double &pm, double &pb)
@@ -66,7 +59,7 @@ k_ht_max(const int32_t *__restrict__ zone, const double *__restrict__ hand, cons
         mm = km > mm ? km : mm;
         mb = kb > mb ? kb : mb;
     }
-    ma = ht_wave_max(ma); mm = ht_wave_max(mm); mb = ht_wave_max(mb); mz = ht_wave_max(mz);
+    ma = wave_max(ma); mm = wave_max(mm); mb = wave_max(mb); mz = wave_max(mz);
     if ((threadIdx.x & 63) == 0) {
         if (ma) atomicMax(ctr + HTC_A, ma);
         if (mm) atomicMax(ctr + HTC_M, mm);
@@ -122,62 +115,29 @@ k_ht_sum(const int32_t *__restrict__ zone, const double *__restrict__ hand, cons
                 atomicAdd(tab + KS * 4 + (key - KS), 1ull);
             continue;
         }
-        u64 todo = __ballot(act);
-        while (todo) {                                          // (todo is the same in every lane)
-            const int leader = __ffsll((long long)todo) - 1;
-            const int64_t lkey = __shfl(key, leader);
-            const bool mine = act && key == lkey;
-            const u64 mask = __ballot(mine);
-            todo &= ~mask;
+        wave_by_key(act, key, [&](int64_t lkey, int leader, u64 mask, bool mine, bool lone) {
             const u64 cnt = (u64)__popcll(mask);
             if (lkey >= KS) {                                   // a NaN / above word: the count alone (uniform branch)
                 if (lane == leader) atomicAdd(tab + KS * 4 + (lkey - KS), cnt);
-                continue;
+                return;
             }
             u64 a = ai, v = mi, b = bi;
-            if (mask != (1ull << leader)) {                     // more than one lane: reduce first (uniform branch)
-                a = ht_wave_add(mine ? ai : 0ull);
-                v = ht_wave_add(mine ? mi : 0ull);
-                b = ht_wave_add(mine ? bi : 0ull);
+            if (!lone) {                                        // more than one lane: reduce first (uniform branch)
+                a = wave_add(mine ? ai : 0ull);
+                v = wave_add(mine ? mi : 0ull);
+                b = wave_add(mine ? bi : 0ull);
             }
             if (lane == leader) {
                 u64 *row = tab + lkey * 4;
                 atomicAdd(row, cnt); atomicAdd(row + 1, a); atomicAdd(row + 2, v); atomicAdd(row + 3, b);
             }
-        }
+        });
     }
-}
-
-double as_double(u64 b)
-{
-    double d;
-    ::memcpy(&d, &b, 8);
-    return d;
-}
-
-struct Events {
-    hipEvent_t e[4] = {};
-    int n = 0;
-    ~Events() { for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]); }
-};
-
-// fraction bits and exponent of a fixed-point sum, as pydem_depressions: B = min(40, 62 - ceil(log2(max(cells, 2)))), E from frexp
-// of the largest term
-void fixed_point(int64_t cells, double largest, int *shift, double *quantum)
-{
-    int lg = 0;
-    const uint64_t x = (uint64_t)(cells < 2 ? 2 : cells) - 1;
-    while (lg < 64 && (x >> lg)) lg++;                  // ceil(log2(x + 1))
-    const int B = 62 - lg < 40 ? 62 - lg : 40;
-    int E = 0;
-    (void)frexp(largest, &E);
-    *shift = B - E;
-    *quantum = ldexp(1.0, E - B);
 }
 
 bool local_reduction()
 {
-    static const bool on = [] { const char *e = getenv("PYDEM_HANDTAB_LOCAL"); return !(e && *e && atoi(e) == 0); }();
+    static const bool on = env_switch("PYDEM_HANDTAB_LOCAL", true);      // (read once per process)
     return on;
 }
 
@@ -206,8 +166,8 @@ int stage_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, con
     const int m = (int)t->m;
     const size_t tab_words = (size_t)K * (size_t)S * 4 + (size_t)K * 2;
 
-    Events ev;
-    for (; ev.n < 4; ev.n++) HIP_TRY(hipEventCreate(&ev.e[ev.n]));
+    Events<4> ev;
+    PYDEM_TRY(ev.create());
     ArenaLease lease;
     PYDEM_TRY(arena_acquire(t->device, &lease));
     // everything the call needs, before any kernel runs
@@ -231,7 +191,7 @@ int stage_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, con
     if (hand) PYDEM_TRY(tile_plane_copy(t, d_hand, const_cast<double *>(hand), (size_t)NN * 8, false));
     PYDEM_TRY(tile_plane_copy(t, d_stages, const_cast<double *>(stages), (size_t)S * 8, false));
 
-    const int gcells = (int)(cdiv(NN, 256) < 8192 ? cdiv(NN, 256) : 8192);
+    const int gcells = capped_grid(NN, GRID_LOOP);
     HIP_TRY(hipMemsetAsync(ctr, 0, HTC_WORDS * 8, t->stream));
     HIP_TRY(hipEventRecord(ev.e[0], t->stream));
     hipLaunchKernelGGL(k_ht_max, dim3(gcells), dim3(256), 0, t->stream, (const int32_t *)d_zone, (const double *)d_hand, (const double *)t->mag,
@@ -271,10 +231,9 @@ int stage_hand_table(pydem_tile *t, const int32_t *zone, const double *hand, con
     }
     if (quanta) for (int k = 0; k < 3; k++) quanta[k] = q[k];
     if (ms) {
-        float a = 0.f, b = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        HIP_TRY(hipEventElapsedTime(&b, ev.e[2], ev.e[3]));
-        ms[0] = (double)a + (double)b; ms[1] = (double)a; ms[2] = (double)b;
+        PYDEM_TRY(ev.elapsed(0, 1, &ms[1]));
+        PYDEM_TRY(ev.elapsed(2, 3, &ms[2]));
+        ms[0] = ms[1] + ms[2];
     }
     return 0;
 }

@@ -14,19 +14,13 @@
 //                   One launch takes a group of consecutive directions (at most HZ_LAUNCH_STEPS steps in all, so that a launch
 //                   stays short on a shared device); the svf sum travels from group to group through its plane, which the
 //                   launches, issued in ascending direction on one stream, read and write: the additions keep their order.
-//   k_hz_total      adds the 64 counter words up.
 // *n_defined: the last launch counts the cells with a finite svf (without an svf, the sum carries 0.0 for a finite tangent and NaN
-// otherwise, so the same test counts the cells with every tangent finite); a wavefront reduction, an integer LDS atomic and one
-// 64-bit integer atomic per workgroup to one of 64 counter words, as terrain.hip does.  The counter, the table, the svf plane and
-// the horizon planes are one block of the tile's (tile_mem.h), grown to the largest request.
-#include "internal.h"
-#include "tile_mem.h"
-#include <math.h>
-#include <vector>
+// otherwise, so the same test counts the cells with every tangent finite) into the slotted counter of stage_kit.h, one atomic per
+// workgroup.  The counter, the table, the svf plane and the horizon planes are one block of the tile's (tile_mem.h), grown to the
+// largest request.
+#include "stage_kit.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int HZ_BR = 32, HZ_BC = 64;       // output rows and columns of a workgroup
 constexpr int HZ_ROWS = HZ_BR / 4;          // rows per lane
@@ -37,7 +31,6 @@ constexpr int HZ_LC = HZ_BC + HZ_SEG + 1;
 constexpr int HZ_LDS = (HZ_BR + HZ_SEG) * HZ_LC;               // doubles
 constexpr int HZ_LAUNCH_STEPS = 512;        // steps of all directions of one launch (one direction at least)
 constexpr int HZ_MAX_DIR = 64, HZ_MAX_STEPS = 1024;
-constexpr int HZ_SLOTS = 64, HZ_SLOT_WORDS = 16, HZ_TOTAL = 8, HZ_CTR_BYTES = HZ_SLOTS * HZ_SLOT_WORDS * 8;
 
 struct HzStep { double w; int off; int pad; };                          // off: (dr - rmin) * HZ_LC + (dc - cmin) in the staged region
 // steps k0 .. k1 - 1 of the device's step list, k1 - k0 a multiple of 4 (padded with steps of weight 0, whose products are zeros
@@ -50,26 +43,13 @@ struct HzArgs {
     int edge_nan, want_svf, first, last;
 };
 
-__device__ __forceinline__ u64 hz_wave_add(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__global__ void __launch_bounds__(64) k_hz_total(u64 *ctr)
-{
-    const u64 sum = hz_wave_add(ctr[(int)threadIdx.x * HZ_SLOT_WORDS]);
-    if (threadIdx.x == 0) ctr[HZ_TOTAL] = sum;
-}
-
 // planes: the n_dir horizon planes, or null; acc: the svf plane, the running sum between launches and the result after the last.
 __global__ void __launch_bounds__(256)
 k_hz(const double *__restrict__ elev, const HzStep *__restrict__ steps, const HzSeg *__restrict__ segs, const HzDir *__restrict__ dirs,
      double *__restrict__ planes, double *__restrict__ accp, u64 *__restrict__ ctr, HzArgs a)
 {
     __shared__ double s_z[HZ_LDS];
-    __shared__ u64 s_count;
-    if (threadIdx.x == 0) s_count = 0;                              // (the barrier before the count comes before its first use)
+    slot_count_begin();
     const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
     const int by = (int)(blockIdx.x / (unsigned)a.blocks_x), bx = (int)(blockIdx.x - (unsigned)by * (unsigned)a.blocks_x);
     const int r0 = by * HZ_BR, c0 = bx * HZ_BC;
@@ -154,19 +134,10 @@ k_hz(const double *__restrict__ elev, const HzStep *__restrict__ steps, const Hz
         }
     }
     if (!a.last) return;                                            // (uniform over the grid; no barrier below on this path)
-    // wavefront, workgroup (an integer LDS atomic), then one global atomic per workgroup
-    mine = hz_wave_add(mine);
-    __syncthreads();
-    if (lane == 0 && mine) atomicAdd(&s_count, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_count) atomicAdd(ctr + (blockIdx.x & (HZ_SLOTS - 1)) * HZ_SLOT_WORDS, s_count);
+    mine = wave_add(mine);
+    __syncthreads();                                                // (directions without steps have no barrier above: the LDS word is zero from here)
+    slot_count(ctr, mine);
 }
-
-struct Events {
-    hipEvent_t e[2] = {};
-    int n = 0;
-    ~Events() { for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]); }
-};
 
 size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 
@@ -227,11 +198,11 @@ int stage_horizon(pydem_tile *t, int n_dir, const int32_t *start, const int16_t 
     const size_t b_steps = round_up(steps.size() * sizeof(HzStep), 256), b_segs = round_up(segs.size() * sizeof(HzSeg), 256),
                  b_dirs = round_up(dirs.size() * sizeof(HzDir), 256);
     const size_t planes = 1 + (horizon ? (size_t)n_dir : 0);
-    const size_t need = HZ_CTR_BYTES + b_steps + b_segs + b_dirs + planes * (size_t)NN * 8;
+    const size_t need = SLOT_BYTES + b_steps + b_segs + b_dirs + planes * (size_t)NN * 8;
     PYDEM_TRY(tile_reserve(t, &t->hz_mem, &t->hz_bytes, need, need, false));
     char *p = (char *)t->hz_mem;
     HzArgs a = {};
-    u64 *ctr = (u64 *)p; p += HZ_CTR_BYTES;
+    u64 *ctr = (u64 *)p; p += SLOT_BYTES;
     HzStep *d_steps = (HzStep *)p; p += b_steps;
     HzSeg *d_segs = (HzSeg *)p; p += b_segs;
     HzDir *d_dirs = (HzDir *)p; p += b_dirs;
@@ -243,9 +214,9 @@ int stage_horizon(pydem_tile *t, int n_dir, const int32_t *start, const int16_t 
     if (!segs.empty()) PYDEM_TRY(tile_plane_copy(t, d_segs, segs.data(), segs.size() * sizeof(HzSeg), false));
     PYDEM_TRY(tile_plane_copy(t, d_dirs, dirs.data(), dirs.size() * sizeof(HzDir), false));
 
-    Events ev;
-    for (; ev.n < 2; ev.n++) HIP_TRY(hipEventCreate(&ev.e[ev.n]));
-    HIP_TRY(hipMemsetAsync(ctr, 0, HZ_CTR_BYTES, t->stream));
+    Events<2> ev;
+    PYDEM_TRY(ev.create());
+    HIP_TRY(hipMemsetAsync(ctr, 0, SLOT_BYTES, t->stream));
     HIP_TRY(hipEventRecord(ev.e[0], t->stream));
     const unsigned blocks = (unsigned)(cdiv(t->n, HZ_BR) * (int64_t)a.blocks_x);
     for (int d0 = 0; d0 < n_dir;) {
@@ -257,19 +228,15 @@ int stage_horizon(pydem_tile *t, int n_dir, const int32_t *start, const int16_t 
         HIP_TRY(hipGetLastError());
         d0 = d1;
     }
-    hipLaunchKernelGGL(k_hz_total, dim3(1), dim3(64), 0, t->stream, ctr);
+    hipLaunchKernelGGL(k_slot_total<>, dim3(1), dim3(64), 0, t->stream, ctr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.e[1], t->stream));
-    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr + HZ_TOTAL, 8, hipMemcpyDeviceToHost, t->stream));       // (the pinned mirror: scratch of every stage)
+    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr + SLOT_TOTAL, 8, hipMemcpyDeviceToHost, t->stream));       // (the pinned mirror: scratch of every stage)
     HIP_TRY(hipStreamSynchronize(t->stream));
     const u64 count = *(volatile u64 *)t->h_counters;
     if (horizon) for (int d = 0; d < n_dir; d++) PYDEM_TRY(tile_plane_copy(t, d_planes + (size_t)d * NN, horizon[d], (size_t)NN * 8, true));
     if (svf) PYDEM_TRY(tile_plane_copy(t, d_acc, svf, (size_t)NN * 8, true));
     if (n_defined) *n_defined = (int64_t)count;
-    if (ms) {
-        float f = 0.f;
-        HIP_TRY(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
-        *ms = (double)f;
-    }
+    if (ms) PYDEM_TRY(ev.elapsed(0, 1, ms));
     return 0;
 }

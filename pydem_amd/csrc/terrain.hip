@@ -19,16 +19,12 @@
 //                    the last half width at which more than half of the staged rows are output rows (16 of 30); K = 8 would
 //                    still fit (65 280 bytes, 14 of 30), K = 9 does not (65 760).  The interface stops at 7.
 // A cell is DEFINED when its window lies inside the tile and M00 is not NaN (a NaN elevation in the window); every requested
-// plane is NaN elsewhere.  *n_defined: every lane counts its defined cells, the wavefront adds them up with xor shuffles, and one
-// 64-bit integer atomic per wavefront (k_ta_march) or per workgroup (k_ta_window, after an integer LDS atomic) goes to one of 64
-// counter words.  No floating-point atomics.  The planes and the counter block are one block of the tile's (tile_mem.h), grown to
-// the largest request.
-#include "internal.h"
-#include <math.h>
+// plane is NaN elsewhere.  *n_defined: every lane counts its defined cells into the slotted counter of stage_kit.h, one 64-bit
+// integer atomic per wavefront (k_ta_march) or per workgroup (k_ta_window).  No floating-point atomics.  The planes and the
+// counter block are one block of the tile's (tile_mem.h), grown to the largest request.
+#include "stage_kit.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int TA_SR = 30;           // staged rows of k_ta_window
 constexpr int TA_COLS = 64;         // its output columns
@@ -118,23 +114,6 @@ __device__ __forceinline__ bool ta_finish(double M00, double M10, double M20, do
     return def;
 }
 
-// The counter block: TA_SLOTS words 128 bytes apart take the atomics (a million additions to ONE address cost 7 ms on the 16384^2
-// tile, more than the arithmetic of a 15 x 15 window), and k_ta_total adds them into the word TA_TOTAL.  Integers: any order gives
-// the same count.
-constexpr int TA_SLOTS = 64, TA_SLOT_WORDS = 16, TA_TOTAL = 8, TA_CTR_BYTES = TA_SLOTS * TA_SLOT_WORDS * 8;
-
-__device__ __forceinline__ u64 ta_wave_add(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__global__ void __launch_bounds__(64) k_ta_total(u64 *ctr)
-{
-    const u64 sum = ta_wave_add(ctr[(int)threadIdx.x * TA_SLOT_WORDS]);
-    if (threadIdx.x == 0) ctr[TA_TOTAL] = sum;
-}
-
 // k = 1.  Wavefront w: strip = w % strips (62 columns), chunk = w / strips (TA_MARCH_ROWS output rows).  Rows and columns off the
 // tile are read clamped and never used: a cell whose window leaves the tile is not `inside`.
 __global__ void __launch_bounds__(256)
@@ -184,8 +163,7 @@ k_ta_march(const double *__restrict__ elev, int n, int m, const double *__restri
         a0 = b0; a1 = b1; a2 = b2; b0 = c0; b1 = c1; b2 = c2;
     }
 #undef TA_ROW
-    mine = ta_wave_add(mine);
-    if (lane == 0 && mine) atomicAdd(ctr + (wid & (TA_SLOTS - 1)) * TA_SLOT_WORDS, mine);
+    slot_count_wave(ctr, mine, wid);
 }
 
 template <int K>
@@ -196,8 +174,7 @@ k_ta_window(const double *__restrict__ elev, int n, int m, const double *__restr
     constexpr int SC = TA_COLS + 2 * K, TR = TA_SR - 2 * K;
     __shared__ double s_z[TA_SR][SC];
     __shared__ double s_r[3][TA_SR][TA_COLS];
-    __shared__ u64 s_count;
-    if (threadIdx.x == 0) s_count = 0;                              // (the barriers below come before its first use)
+    slot_count_begin();                                             // (the barriers below come before the count)
     const int by = (int)(blockIdx.x / (unsigned)blocks_x), bx = (int)(blockIdx.x - (unsigned)by * (unsigned)blocks_x);
     const int r0 = by * TR, c0 = bx * TA_COLS;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -241,18 +218,8 @@ k_ta_window(const double *__restrict__ elev, int n, int m, const double *__restr
         if (gr < n && gc < m)
             mine += ta_finish(M00, M10, M20, M01, M02, M11, true, dX2[gr], dY2[gr], k, o, (size_t)gr * m + gc) ? 1u : 0u;
     }
-    // wavefront, workgroup (an integer LDS atomic), then one global atomic per workgroup
-    mine = ta_wave_add(mine);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_count, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_count) atomicAdd(ctr + (blockIdx.x & (TA_SLOTS - 1)) * TA_SLOT_WORDS, s_count);
+    slot_count(ctr, wave_add(mine));
 }
-
-struct Events {
-    hipEvent_t e[2] = {};
-    int n = 0;
-    ~Events() { for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]); }
-};
 
 template <int K>
 void launch_window(pydem_tile *t, const TaConst &k, const TaOuts &o, u64 *ctr)
@@ -260,12 +227,6 @@ void launch_window(pydem_tile *t, const TaConst &k, const TaOuts &o, u64 *ctr)
     const int64_t bx = cdiv(t->m, TA_COLS), by = cdiv(t->n, TA_SR - 2 * K);
     hipLaunchKernelGGL((k_ta_window<K>), dim3((unsigned)(bx * by)), dim3(256), 0, t->stream, (const double *)t->elev, (int)t->n, (int)t->m,
                        (const double *)t->dX2, (const double *)t->dY2, (int)bx, k, o, ctr);
-}
-
-bool force_generic()        // PYDEM_TA_GENERIC=1 (read per call: the tests switch it): k = 1 through k_ta_window too
-{
-    const char *e = getenv("PYDEM_TA_GENERIC");
-    return e && *e && atoi(e) != 0;
 }
 
 }  // namespace
@@ -296,22 +257,22 @@ int stage_terrain_attributes(pydem_tile *t, int half_width, const double *light,
     k.zf = z_factor;
 
     // one block: the counter block (8192 bytes), then the requested planes
-    const size_t need = TA_CTR_BYTES + (size_t)wanted * (size_t)NN * 8;
+    const size_t need = SLOT_BYTES + (size_t)wanted * (size_t)NN * 8;
     PYDEM_TRY(tile_reserve(t, &t->ta_mem, &t->ta_bytes, need, need, false));
     u64 *ctr = (u64 *)t->ta_mem;
     TaOuts o;
     {
-        double *next = (double *)((char *)t->ta_mem + TA_CTR_BYTES);
+        double *next = (double *)((char *)t->ta_mem + SLOT_BYTES);
         for (int a = 0; a < PYDEM_TA_COUNT; a++) {
             o.p[a] = outs[a] ? next : nullptr;
             if (outs[a]) next += NN;
         }
     }
-    Events ev;
-    for (; ev.n < 2; ev.n++) HIP_TRY(hipEventCreate(&ev.e[ev.n]));
-    HIP_TRY(hipMemsetAsync(ctr, 0, TA_CTR_BYTES, t->stream));
+    Events<2> ev;
+    PYDEM_TRY(ev.create());
+    HIP_TRY(hipMemsetAsync(ctr, 0, SLOT_BYTES, t->stream));
     HIP_TRY(hipEventRecord(ev.e[0], t->stream));
-    if (half_width == 1 && !force_generic()) {
+    if (half_width == 1 && !env_switch("PYDEM_TA_GENERIC", false)) {     // (read per call: the tests switch it) k = 1 through k_ta_window too
         const int64_t strips = cdiv(t->m, 62), chunks = cdiv(t->n, TA_MARCH_ROWS);
         hipLaunchKernelGGL(k_ta_march, dim3((unsigned)cdiv(strips * chunks, 4)), dim3(256), 0, t->stream, (const double *)t->elev, (int)t->n,
                            (int)t->m, (const double *)t->dX2, (const double *)t->dY2, (int)strips, (int)chunks, k, o, ctr);
@@ -327,19 +288,15 @@ int stage_terrain_attributes(pydem_tile *t, int half_width, const double *light,
         }
     }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_ta_total, dim3(1), dim3(64), 0, t->stream, ctr);
+    hipLaunchKernelGGL(k_slot_total<>, dim3(1), dim3(64), 0, t->stream, ctr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.e[1], t->stream));
-    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr + TA_TOTAL, 8, hipMemcpyDeviceToHost, t->stream));      // (the pinned mirror: scratch of every stage)
+    HIP_TRY(hipMemcpyAsync(t->h_counters, ctr + SLOT_TOTAL, 8, hipMemcpyDeviceToHost, t->stream));      // (the pinned mirror: scratch of every stage)
     HIP_TRY(hipStreamSynchronize(t->stream));
     const u64 count = *(volatile u64 *)t->h_counters;
     for (int a = 0; a < PYDEM_TA_COUNT; a++)
         if (outs[a]) PYDEM_TRY(tile_plane_copy(t, o.p[a], outs[a], (size_t)NN * 8, true));
     if (n_defined) *n_defined = (int64_t)count;
-    if (ms) {
-        float f = 0.f;
-        HIP_TRY(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
-        *ms = (double)f;
-    }
+    if (ms) PYDEM_TRY(ev.elapsed(0, 1, ms));
     return 0;
 }

@@ -1,5 +1,6 @@
 // tile.hip -- handle management, spacing tables, upload/download and the extern "C" surface.
 #include "internal.h"
+#include "line_gather.h"
 #include "uca_graph.h"      // CI_STATIC_MASK, CS_FLAT_SAVE
 #include <cmath>
 #include <stdarg.h>
@@ -17,12 +18,7 @@ void pydem_set_error(const char *fmt, ...)
 
 namespace {
 
-template <typename T>
-__global__ void k_line_gather(const T *__restrict__ src, int64_t stride, int64_t count, T *__restrict__ dst)
-{
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) dst[k] = src[k * stride];
-}
-template <typename T>
+template <typename T>      // (its counterpart k_line_gather: line_gather.h)
 __global__ void k_line_scatter(const T *__restrict__ src, int64_t stride, int64_t count, T *__restrict__ dst)
 {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) dst[k * stride] = src[k];

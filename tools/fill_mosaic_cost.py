@@ -15,14 +15,13 @@ csrc/fill_depressions.hip, each rewritten by its own mode and kept by the other,
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
 import time
 import warnings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from kernel_resources import kernel_resources      # (tools/ is the script directory)
 
 MEASURED, COMPILER, NOTES = '== measurement ==', '== compiler report ==', '== notes =='
 
@@ -93,27 +92,11 @@ def measure(n):
 
 def compiler_report():
     from pydem_amd import build
-    src = os.path.join(build.CSRC, 'fill_depressions.hip')
-    out = subprocess.run([build.HIPCC] + build.FLAGS + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', os.devnull],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, check=True).stdout
-    def kernel(mangled):
-        """k_fd_relax_seam<true> from _ZN12_GLOBAL__N_115k_fd_relax_seamILb1EEEv... (the kernels' names are lower case)"""
-        m = re.match(r'_ZN12_GLOBAL__N_1\d+([a-z_]+)(?:ILb([01])E)?E', mangled)
-        return mangled if not m else m.group(1) + ('' if m.group(2) is None else '<%s>' % ('true' if m.group(2) == '1' else 'false'))
-    rows, cur = [], None
-    for line in out.splitlines():
-        m = re.search(r'remark: +(Function Name|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (.*?) \[-Rpass', line)
-        if not m:
-            continue
-        if m.group(1) == 'Function Name':
-            cur = {'name': kernel(m.group(2))}
-            rows.append(cur)
-        elif cur is not None:
-            cur[m.group(1).split(' ')[0]] = m.group(2)
+    rows = kernel_resources('fill_depressions.hip')
     text = ["hipcc %s, -Rpass-analysis=kernel-resource-usage" % ' '.join(build.FLAGS)]
-    for r in sorted(rows, key=lambda r: r['name']):
+    for name, r in sorted(rows.items()):
         text.append("%-34s %3s VGPRs, scratch %s B/lane, LDS %5s B per workgroup, %s wavefronts per SIMD"
-                    % (r['name'], r.get('VGPRs'), r.get('ScratchSize'), r.get('LDS'), r.get('Occupancy')))
+                    % (name, r['vgprs'], r['scratch'], r['lds'], r['occupancy']))
     return '\n'.join(text)
 
 

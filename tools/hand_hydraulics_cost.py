@@ -16,10 +16,7 @@ it."""
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
-import tempfile
 import time
 import warnings
 
@@ -27,27 +24,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def kernel_resources():
-    """{kernel: {sgprs, vgprs, scratch, occupancy, lds}} of csrc/hand_table.hip from -Rpass-analysis=kernel-resource-usage"""
-    from pydem_amd import build
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build.HIPCC] + build.FLAGS + ['-Rpass-analysis=kernel-resource-usage', '-c',
-                                                          os.path.join(build.CSRC, 'hand_table.hip'), '-o', os.path.join(tmp, 'x.o')],
-                           capture_output=True, text=True, check=True)
-    out, cur = {}, None
-    keys = {'TotalSGPRs': 'sgprs', 'VGPRs': 'vgprs', 'ScratchSize [bytes/lane]': 'scratch', 'Occupancy [waves/SIMD]': 'occupancy',
-            'LDS Size [bytes/block]': 'lds'}
-    for line in r.stderr.splitlines():
-        m = re.search(r'Function Name: \S*?(k_ht_[a-z]+)', line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-        for k, v in keys.items():
-            m = re.search(r'remark:\s+%s: (\d+)' % re.escape(k), line)
-            if m and cur is not None:
-                cur[v] = int(m.group(1))
-    return out
+from kernel_resources import kernel_resources      # (tools/ is the script directory)
 
 
 def main():
@@ -62,7 +39,7 @@ def main():
     args = ap.parse_args()
     out = {}
     if args.resources:
-        out['kernel_resources'] = kernel_resources()
+        out['kernel_resources'] = kernel_resources('hand_table.hip')
     if args.size > 0:
         from pydem_amd import DEMProcessor
         warnings.simplefilter('ignore')

@@ -14,41 +14,18 @@ no device; --size 0 skips the device part).  Appends one JSON line to `--out` an
 import argparse
 import json
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
 import warnings
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from kernel_resources import kernel_resources      # (tools/ is the script directory)
 
 LDS_BYTES_PER_S = 256 * 256 * 2.4e9         # CUs x bytes per clock and CU (ds_read_b64) x clock
 RUNS = (('svf_8_dirs_32_cells', 8, 32), ('svf_16_dirs_100_cells', 16, 100), ('shadow_1_dir_100_cells', 1, 100))
-
-
-def kernel_resources():
-    """{kernel: {sgprs, vgprs, scratch, occupancy, lds}} of csrc/horizon.hip from -Rpass-analysis=kernel-resource-usage"""
-    from pydem_amd import build
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build.HIPCC] + build.FLAGS + ['-Rpass-analysis=kernel-resource-usage', '-c',
-                                                          os.path.join(build.CSRC, 'horizon.hip'), '-o', os.path.join(tmp, 'x.o')],
-                           capture_output=True, text=True, check=True)
-    out, cur = {}, None
-    keys = {'TotalSGPRs': 'sgprs', 'VGPRs': 'vgprs', 'ScratchSize [bytes/lane]': 'scratch', 'Occupancy [waves/SIMD]': 'occupancy',
-            'LDS Size [bytes/block]': 'lds'}
-    for line in r.stderr.splitlines():
-        m = re.search(r'Function Name: \S*?\d(k_hz_total|k_hz)E', line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-        for k, v in keys.items():
-            m = re.search(r'remark:\s+%s: (\d+)' % re.escape(k), line)
-            if m and cur is not None:
-                cur[v] = int(m.group(1))
-    return out
 
 
 def main():
@@ -62,7 +39,7 @@ def main():
         ap.error("--repeats must be at least 10: the figure is a median of warm runs")
     out = {}
     if args.resources:
-        out['kernel_resources'] = kernel_resources()
+        out['kernel_resources'] = kernel_resources('horizon.hip')
     if args.size > 0:
         from pydem_amd import DEMProcessor, horizon
         warnings.simplefilter('ignore')

@@ -13,38 +13,15 @@ csrc/terrain.hip alone; needs no device; --size 0 skips the device part).  Appen
 import argparse
 import json
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
 import warnings
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def kernel_resources():
-    """{kernel: {sgprs, vgprs, scratch, occupancy, lds}} of csrc/terrain.hip from -Rpass-analysis=kernel-resource-usage"""
-    from pydem_amd import build
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build.HIPCC] + build.FLAGS + ['-Rpass-analysis=kernel-resource-usage', '-c',
-                                                          os.path.join(build.CSRC, 'terrain.hip'), '-o', os.path.join(tmp, 'x.o')],
-                           capture_output=True, text=True, check=True)
-    out, cur = {}, None
-    keys = {'TotalSGPRs': 'sgprs', 'VGPRs': 'vgprs', 'ScratchSize [bytes/lane]': 'scratch', 'Occupancy [waves/SIMD]': 'occupancy',
-            'LDS Size [bytes/block]': 'lds'}
-    for line in r.stderr.splitlines():
-        m = re.search(r'Function Name: \S*?(k_ta_march|k_ta_total|k_ta_windowILi(\d)E)', line)
-        if m:
-            cur = out.setdefault('k_ta_window<%s>' % m.group(2) if m.group(2) else m.group(1), {})
-        for k, v in keys.items():
-            m = re.search(r'remark:\s+%s: (\d+)' % re.escape(k), line)
-            if m and cur is not None:
-                cur[v] = int(m.group(1))
-    return out
+from kernel_resources import kernel_resources      # (tools/ is the script directory)
 
 
 def main():
@@ -58,7 +35,7 @@ def main():
         ap.error("--repeats must be at least 10: the figure is a median of warm runs")
     out = {}
     if args.resources:
-        out['kernel_resources'] = kernel_resources()
+        out['kernel_resources'] = kernel_resources('terrain.hip')
     if args.size > 0:
         from pydem_amd import DEMProcessor, terrain
         warnings.simplefilter('ignore')
