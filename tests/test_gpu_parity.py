@@ -304,9 +304,12 @@ def test_config1_cone256_device_vs_reference_pinned_oracle():
     _close(dp.mag, o.mag, 'mag'); _close(dp.direction, o.direction, 'direction'); _close(dp.uca, o.uca, 'uca'); _close(twi, twi_o, 'twi')
 
 
-def assert_edge_set_equals_oracle(o, dp):
+def assert_edge_set_equals_oracle(o, dp, exact=False):
     """The edge set the device's graph words and pit list describe (after calc_uca) against the oracle's CSC triplets o.A:
-    the same (source, target) pairs exactly, weights within RTOL, and every regular edge present in its target's in-mask."""
+    the same (source, target) pairs exactly, weights within RTOL, and every regular edge present in its target's in-mask.  A
+    regular edge's weight is formed HERE, as proportion or 1 - proportion of the device's proportion plane; exact=True asks that
+    it equal the oracle's (which follows once the proportion bits and the edge set are the oracle's: it says that the word's
+    flags pair each share with the right target).  The 1 - proportion the sweep forms on the device is seen through uca."""
     n, m = o.elev.shape
     z = np.asarray(o.elev, np.float64)
     indptr, indices, data = o.A
@@ -335,6 +338,10 @@ def assert_edge_set_equals_oracle(o, dp):
     assert set(dev) == set(ref), (len(dev), len(ref), sorted(set(dev) ^ set(ref))[:5])
     worst = max(abs(dev[k] - ref[k]) / max(abs(ref[k]), 1e-300) for k in ref)
     assert worst <= RTOL, worst
+    if exact:
+        pit_pairs = set(zip(ps[keep].tolist(), pd[keep].tolist()))              # (a pit edge's weight is the pit search's: RTOL above)
+        off = [k for k in ref if k not in pit_pairs and dev[k] != ref[k]]
+        assert not off, (len(off), off[:5])
     # the in-mask of a target holds the bit of every regular edge into it (bit order NW N NE W E SW S SE)
     nb = {(-1, -1): 0, (-1, 0): 1, (-1, 1): 2, (0, -1): 3, (0, 1): 4, (1, -1): 5, (1, 0): 6, (1, 1): 7}
     inmask = np.zeros(n * m, np.uint32)
